@@ -3,6 +3,7 @@
 gradient all-reduce + fused Adam) at 320x320, L=20, B=8 per GPU, synthetic data.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_out/run1   # + the last timed step's outputs as .npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -216,6 +217,34 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_SAMPLE = 1 << 21        # elements of the flat parameter / gradient buffers kept by --dump-outputs (8 MB each as float32)
+DUMP_LIMIT = 64 << 20        # bytes written by --dump-outputs, all files together
+
+
+def dump_outputs(model, step, scal, out_dir):
+    """--dump-outputs: what the LAST timed train step computed, as float32 / float64 .npy files, so that two builds can be compared
+    output for output: the scalars train_step returned (losses, mean IoU, learning rate, global step), its forward fetches (pred, up,
+    sigm) and a fixed, seeded sample of the updated parameters and of the step's gradients (loss scale divided out; the full flat
+    buffers hold ~76M elements each)."""
+    torch.cuda.synchronize()
+    eng = model.eng
+    out = {"global_step": np.float64(step)}
+    out.update({k: np.float64(float(v)) for k, v in scal.items()})
+    for k in ("pred", "up", "sigm"):
+        out[k] = eng.tap(k).detach().float().cpu().numpy()
+    idx = np.sort(np.random.default_rng(0).choice(eng.total, size=min(DUMP_SAMPLE, eng.total), replace=False))
+    ix = torch.from_numpy(idx).to(eng.params.device)
+    out["params_sample"] = eng.params[ix].float().cpu().numpy()
+    out["grads_sample"] = (eng.grads[ix].double() / eng.loss_scale).float().cpu().numpy()
+    nbytes = sum(a.nbytes for a in out.values())
+    if nbytes > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {nbytes} bytes exceed the {DUMP_LIMIT} byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    log(f"dumped {len(out)} arrays ({nbytes / 2**20:.1f} MB) of the last timed step to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -238,7 +267,12 @@ def main():
                     "of at the start of its own step (measured SLOWER: 11.2 vs 10.5 ms, DESIGN 7; off by default)")
     ap.add_argument("--no-config4", action="store_true", help="skip the BASELINE config 4 rate reported inside the default line")
     ap.add_argument("--no-config5", action="store_true", help="skip the BASELINE config 5 (video) rate reported inside the default line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MB; rank 0). "
+                         "bench_out/<tag> is ignored by git")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -296,9 +330,11 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, scal = model.train_step(words, im, target, seq_len, ready=ready, **nxt)
+        gstep, scal = model.train_step(words, im, target, seq_len, ready=ready, **nxt)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, gstep, scal, args.dump_outputs)
     loss = float(scal["loss_all"])
     launches = model.eng.launch_count()            # library launches of the last forward + backward + optimizer step
     # Per-launch timing of the dominant kernel family: in the timed region above the three pyramid levels run on three

@@ -1,5 +1,6 @@
 #!/bin/bash
-# A/B of the step schedule on one box: prefetch of the next batch's backbone (behind the levels' forward) x lanes x hardware queues.
+# A/B of the step schedule on one box: prefetch of the next batch's backbone (behind the levels' forward) x lanes, at the runtime's
+# default hardware-queue count (raising GPU_MAX_HW_QUEUES is not done on shared machines).
 cd $GRAFT_REPO_ROOT
 run() { # label, env..., -- bench args
   label=$1; shift
@@ -11,8 +12,4 @@ EXTRA="" run "base  lanes3 q4" CMPC_STREAMS=3
 EXTRA="--prefetch"            run "pref  lanes3 q4" CMPC_STREAMS=3
 EXTRA="--prefetch"            run "pref  lanes2 q4" CMPC_STREAMS=2
 EXTRA="" run "base  lanes2 q4" CMPC_STREAMS=2
-EXTRA="--prefetch"            run "pref  lanes3 q8" CMPC_STREAMS=3 GPU_MAX_HW_QUEUES=8
-EXTRA="--prefetch"            run "pref  lanes2 q8" CMPC_STREAMS=2 GPU_MAX_HW_QUEUES=8
-EXTRA="" run "base  lanes2 q8" CMPC_STREAMS=2 GPU_MAX_HW_QUEUES=8
-EXTRA="--prefetch"            run "pref  lanes2 q6" CMPC_STREAMS=2 GPU_MAX_HW_QUEUES=6
 done
