@@ -114,6 +114,16 @@ class Feeds(C.Structure):
                 ("target_fine", C.c_void_p), ("feats_ready", C.c_void_p), ("c2", C.c_void_p), ("im", C.c_void_p), ("feats_ready_lv", C.c_void_p * 3), ("levels_done", C.c_void_p)]
 
 
+class EvalDesc(C.Structure):
+    """cmpc_eval_desc"""
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int), ("w", C.c_int), ("c", C.c_int),
+                ("rh", C.c_int), ("rw", C.c_int), ("top", C.c_int), ("left", C.c_int), ("pad_", C.c_int)]
+
+
+EVAL_MAX_BATCH = 32      # CMPC_EVAL_MAX_BATCH
+EVAL_F32, EVAL_U8 = 0, 1
+
+
 class Fetches(C.Structure):
     """cmpc_fetches"""
     _fields_ = [("pred", C.c_void_p), ("up", C.c_void_p), ("sigm", C.c_void_p)]
@@ -221,6 +231,8 @@ SIGNATURES = {
     "cmpc_phase_marks_read": [_P, _I, C.POINTER(C.c_char_p), C.POINTER(C.c_float)],
     "cmpc_set_lanes": [_P, _I],
     "cmpc_dense_crf": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P],
+    "cmpc_eval_prep": [_P, _L, C.POINTER(EvalDesc), _I, _I, _I, _P, _P, _P],
+    "cmpc_eval_mask_iu": [_P, _I, _I, _I, _I, _F, _P, _L, C.POINTER(EvalDesc), _P, _P, _P],
     "cmpc_launch_trace": [_I, _P],
     "cmpc_launch_trace_read": [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_L)],
     "cmpc_kernel_timing": [_P, _I],

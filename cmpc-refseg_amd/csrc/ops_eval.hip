@@ -1,0 +1,370 @@
+// Evaluation-side image and mask resampling of the reference's `-m test` loop (trainval_model.py:227-303):
+//
+//   eval_prep     proc_im = img_as_ubyte(resize_and_pad(im, H, W)); feed = proc_im[..., ::-1].astype(float32) - mu
+//   eval_mask_iu  I, U of resize_and_crop(up >= thresh, mh, mw) against the ground truth at its original size
+//
+// The resampler is skimage.transform.resize as cmpc-refseg_amd/hostutil.py restates it on scipy.ndimage: a mirror-mode Gaussian
+// (sigma = (f - 1) / 2, radius int(4 sigma + 0.5)) on every shrinking axis, then ndimage.zoom(order=1, mode="mirror", grid_mode=True).
+// eval_prep repeats SciPy's float64 arithmetic operation for operation (file-wide contract(off): no fused multiply-adds):
+//   - correlate1d's symmetric form  out = x[0] w[0] + sum_{d=r..1} (x[-d] + x[+d]) w[d]   (axis 0, then axis 1)
+//   - the zoom's source coordinate  cc = (o + 0.5) (in / out) - 0.5, reflected about 0 when negative; taps floor(cc), floor(cc) + 1
+//     (mirrored indices) with weights 1 - t and 1 - (1 - t); the four products ((v wy) wx) summed in row-major tap order
+// so proc_im equals the host's bytes except where the device's exp() rounds a Gaussian weight differently from NumPy's.
+// eval_mask_iu needs no arithmetic at all: every Gaussian weight inside the radius is positive and the bilinear weight 1 - (1 - t) is
+// zero exactly when SciPy's is, so "resampled value > 0" is the OR of the binarised map over the taps with non-zero weight.
+#include "cmpc_common.h"
+#include "../../include/cmpc.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int MAXR = 63;                 // Gaussian radius limit (shrink factors up to ~32)
+constexpr int NTHR = 256;
+
+struct SampleGeo {                       // host-derived per-sample constants (passed by value)
+    double zy, zx;                       // source / resized, float64 (ndimage.zoom's factors)
+    double sy, sx;                       // Gaussian sigmas (0: axis not blurred)
+    int ry, rx;                          // radii
+};
+
+struct PrepArgs {
+    const unsigned char* src; int64_t src_bytes;
+    unsigned char* proc; float* feed;
+    int H, W, B, ty, tx, tiles_x, tiles;
+    cmpc_eval_desc d[CMPC_EVAL_MAX_BATCH];
+    SampleGeo g[CMPC_EVAL_MAX_BATCH];
+};
+
+struct MaskArgs {
+    const void* map; int map_dt; int H, W, B; float thresh;
+    const unsigned char* gt; unsigned char* mask_out;
+    unsigned long long* iu;
+    cmpc_eval_desc d[CMPC_EVAL_MAX_BATCH];
+    SampleGeo g[CMPC_EVAL_MAX_BATCH];
+};
+
+__device__ __forceinline__ int mirror_idx(int i, int n) {
+    if (n == 1) return 0;
+    const int p = 2 * (n - 1);
+    i = abs(i) % p;
+    return i >= n ? p - i : i;
+}
+
+// SciPy's zoom source coordinate for output index o (grid_mode, mirror): taps i0, i1 and weights w0 = 1 - t, w1 = 1 - (1 - t)
+__device__ __forceinline__ void zoom_taps(int o, double z, int n, int& i0, int& i1, double& w0, double& w1) {
+    double cc = ((double)o + 0.5) * z - 0.5;
+    if (n == 1) cc = 0.0;
+    else if (cc < 0.0) cc = -cc;
+    const double f = floor(cc);
+    const double t = cc - f;
+    w0 = 1.0 - t;
+    w1 = 1.0 - w0;
+    i0 = mirror_idx((int)f, n);
+    i1 = mirror_idx((int)f + 1, n);
+}
+
+// _gaussian_kernel1d(sigma, 0, r) normalised by NumPy's pairwise sum; w[d] for d = 0..r (symmetric)
+__device__ void gauss_weights(double sigma, int r, double* w) {
+    double phi[2 * MAXR + 1];
+    const int n = 2 * r + 1;
+    const double a = -0.5 / (sigma * sigma);
+    for (int i = 0; i < n; ++i) { const double x = (double)((i - r) * (i - r)); phi[i] = exp(a * x); }
+    double s;
+    if (n < 8) {
+        s = 0.0;
+        for (int i = 0; i < n; ++i) s += phi[i];
+    } else {
+        double p[8];
+        for (int j = 0; j < 8; ++j) p[j] = phi[j];
+        int i = 8;
+        for (; i < n - (n % 8); i += 8)
+            for (int j = 0; j < 8; ++j) p[j] += phi[i + j];
+        s = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+        for (; i < n; ++i) s += phi[i];
+    }
+    for (int d = 0; d <= r; ++d) w[d] = phi[r + d] / s;
+}
+
+// LDS footprint (bytes) of one tile: raw uint8 rows [ny + 2 ry][nx + 2 rx][c] + vertical pass [ny][nx + 2 rx][c] float64
+__host__ __device__ inline void tile_extent(double z, int t, int r, int n, int& span, int& span_r) {
+    span = (int)ceil((double)(t - 1) * z) + 6;
+    if (span > n + 2) span = n + 2;
+    span_r = span + 2 * r;
+}
+
+__global__ __launch_bounds__(NTHR) void eval_prep_kernel(PrepArgs a) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    __shared__ double wy[MAXR + 1], wx[MAXR + 1];
+    const int b = blockIdx.y;
+    const cmpc_eval_desc d = a.d[b];
+    const SampleGeo g = a.g[b];
+    const int C = d.c, h = d.h, w = d.w;
+    if (threadIdx.x == 0) {
+        if (g.sy > 0.0) gauss_weights(g.sy, g.ry, wy);
+        if (g.sx > 0.0) gauss_weights(g.sx, g.rx, wx);
+    }
+    int NYb, NYr, NXb, NXr;
+    tile_extent(g.zy, a.ty, g.ry, h, NYb, NYr);
+    tile_extent(g.zx, a.tx, g.rx, w, NXb, NXr);
+    unsigned char* raw = lds;                                                       // [NYr][NXr][C]
+    double* vy = (double*)(lds + (((size_t)NYr * NXr * C + 15) & ~(size_t)15));      // [NYb][NXr][C]
+    const unsigned char* src = a.src + d.offset;
+    const double mu[3] = {104.00698793, 116.66876762, 122.67891434};               // trainval_model.py:371 (B, G, R)
+    __syncthreads();
+
+    for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+        const int oy0 = (tile / a.tiles_x) * a.ty, ox0 = (tile % a.tiles_x) * a.tx;
+        // the tile's part of the resized rectangle, in resized coordinates
+        const int ya = max(oy0 - d.top, 0), yb = min(oy0 + a.ty - d.top, d.rh);
+        const int xa = max(ox0 - d.left, 0), xb = min(ox0 + a.tx - d.left, d.rw);
+        const bool any = ya < yb && xa < xb;
+        int lo_y = 0, lo_x = 0, ny = 0, nx = 0;
+        if (any) {
+            // source rows / columns the bilinear taps can reach (one extra on each side covers the reflections at the edges)
+            lo_y = max(0, (int)floor(((double)ya + 0.5) * g.zy - 0.5) - 1);
+            lo_x = max(0, (int)floor(((double)xa + 0.5) * g.zx - 0.5) - 1);
+            ny = min(h - 1, (int)floor(((double)(yb - 1) + 0.5) * g.zy - 0.5) + 2) - lo_y + 1;
+            nx = min(w - 1, (int)floor(((double)(xb - 1) + 0.5) * g.zx - 0.5) + 2) - lo_x + 1;
+            ny = min(ny, NYb); nx = min(nx, NXb);           // never binding (tile_extent has slack): keeps LDS indexing in range
+            const int nyr = ny + 2 * g.ry, nxr = nx + 2 * g.rx;
+            const int rowb = nxr * C;
+            // stage the mirrored footprint: consecutive threads take consecutive bytes of a source row
+            for (int i = threadIdx.x; i < nyr * rowb; i += NTHR) {
+                const int r = i / rowb, k = i - r * rowb;
+                const int col = k / C, ch = k - col * C;
+                const int sy = mirror_idx(lo_y - g.ry + r, h), sx = mirror_idx(lo_x - g.rx + col, w);
+                raw[r * NXr * C + k] = src[((int64_t)sy * w + sx) * C + ch];
+            }
+            __syncthreads();
+            // axis 0: correlate1d (or the plain img_as_float value when the axis is not blurred)
+            for (int i = threadIdx.x; i < ny * rowb; i += NTHR) {
+                const int r = i / rowb, k = i - r * rowb;
+                const unsigned char* col = raw + (r + g.ry) * NXr * C + k;
+                double acc;
+                if (g.sy > 0.0) {
+                    acc = ((double)col[0] / 255.0) * wy[0];
+                    for (int dd = g.ry; dd >= 1; --dd)
+                        acc = acc + (((double)col[-dd * NXr * C] / 255.0) + ((double)col[dd * NXr * C] / 255.0)) * wy[dd];
+                } else {
+                    acc = (double)col[0] / 255.0;
+                }
+                vy[r * NXr * C + k] = acc;
+            }
+            __syncthreads();
+        }
+        const int ly = threadIdx.x / a.tx, lx = threadIdx.x - ly * a.tx;
+        const int oy = oy0 + ly, ox = ox0 + lx;
+        if (ly < a.ty && oy < a.H && ox < a.W) {
+            const int y = oy - d.top, x = ox - d.left;
+            unsigned char q[3] = {0, 0, 0};
+            if (any && y >= 0 && y < d.rh && x >= 0 && x < d.rw) {
+                int y0, y1, x0, x1; double wy0, wy1, wx0, wx1;
+                zoom_taps(y, g.zy, h, y0, y1, wy0, wy1);
+                zoom_taps(x, g.zx, w, x0, x1, wx0, wx1);
+                const int ys[2] = {y0 - lo_y, y1 - lo_y}, xs[2] = {x0 - lo_x + g.rx, x1 - lo_x + g.rx};
+                const double wys[2] = {wy0, wy1}, wxs[2] = {wx0, wx1};
+                for (int c = 0; c < C; ++c) {
+                    double t = 0.0;
+                    for (int iy = 0; iy < 2; ++iy)
+                        for (int ix = 0; ix < 2; ++ix) {
+                            const double* row = vy + ys[iy] * NXr * C + c;
+                            const int cx = xs[ix];
+                            double v;
+                            if (g.sx > 0.0) {           // axis 1: correlate1d on the vertical pass
+                                v = row[cx * C] * wx[0];
+                                for (int dd = g.rx; dd >= 1; --dd) v = v + (row[(cx - dd) * C] + row[(cx + dd) * C]) * wx[dd];
+                            } else {
+                                v = row[cx * C];
+                            }
+                            t = t + (v * wys[iy]) * wxs[ix];
+                        }
+                    const double s = rint(t * 255.0);                        // img_as_ubyte
+                    q[c] = (unsigned char)fmin(fmax(s, 0.0), 255.0);
+                }
+                if (C == 1) q[1] = q[2] = q[0];                              // build_batches.py:67-68
+            }
+            const int64_t o = (((int64_t)b * a.H + oy) * a.W + ox) * 3;
+            a.proc[o] = q[0]; a.proc[o + 1] = q[1]; a.proc[o + 2] = q[2];
+            // proc_im[..., ::-1].astype(float32) -= mu: a float64 subtract rounded once to float32
+            a.feed[o] = (float)((double)q[2] - mu[0]);
+            a.feed[o + 1] = (float)((double)q[1] - mu[1]);
+            a.feed[o + 2] = (float)((double)q[0] - mu[2]);
+        }
+        __syncthreads();                                    // the next tile overwrites raw / vy
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ bool fg(const T* m, int W, int y, int x, float th) { return (float)m[(int64_t)y * W + x] >= th; }
+
+// foreground of the resampled binarised map at resized position (oy, ox): OR over the non-zero-weight taps of the blurred window
+template <typename T>
+__device__ bool pred_at(const T* m, int H, int W, float th, const SampleGeo& g, int oy, int ox) {
+    int y0, y1, x0, x1; double wy0, wy1, wx0, wx1;
+    zoom_taps(oy, g.zy, H, y0, y1, wy0, wy1);
+    zoom_taps(ox, g.zx, W, x0, x1, wx0, wx1);
+    const int ty[2] = {y0, y1}, tx[2] = {x0, x1};
+    const int ny = wy1 != 0.0 ? 2 : 1, nx = wx1 != 0.0 ? 2 : 1;        // w0 = 1 - t is never 0
+    const int ry = g.sy > 0.0 ? g.ry : 0, rx = g.sx > 0.0 ? g.rx : 0;
+    for (int iy = 0; iy < ny; ++iy)
+        for (int ix = 0; ix < nx; ++ix)
+            for (int dy = -ry; dy <= ry; ++dy) {
+                const int yy = mirror_idx(ty[iy] + dy, H);
+                for (int dx = -rx; dx <= rx; ++dx)
+                    if (fg(m, W, yy, mirror_idx(tx[ix] + dx, W), th)) return true;
+            }
+    return false;
+}
+
+template <typename T>
+__global__ __launch_bounds__(NTHR) void eval_mask_iu_kernel(MaskArgs a) {
+    const int b = blockIdx.y;
+    const cmpc_eval_desc d = a.d[b];
+    const SampleGeo g = a.g[b];
+    const T* m = (const T*)a.map + (int64_t)b * a.H * a.W;
+    const unsigned char* gt = a.gt + d.offset;
+    unsigned char* mo = a.mask_out ? a.mask_out + d.offset : nullptr;
+    const int64_t n = (int64_t)d.h * d.w;
+    const bool al_gt = (d.offset & 3) == 0;
+    unsigned long long I = 0, U = 0;
+    for (int64_t i4 = ((int64_t)blockIdx.x * NTHR + threadIdx.x) * 4; i4 < n; i4 += (int64_t)gridDim.x * NTHR * 4) {
+        const int k = (int)min((int64_t)4, n - i4);
+        uint32_t gv = 0;
+        if (k == 4 && al_gt) gv = *(const uint32_t*)(gt + i4);                // 4 ground-truth bytes per load
+        else for (int j = 0; j < k; ++j) gv |= (uint32_t)gt[i4 + j] << (8 * j);
+        uint32_t pv = 0;
+        for (int j = 0; j < k; ++j) {
+            const int64_t i = i4 + j;
+            const int y = (int)(i / d.w), x = (int)(i - (int64_t)y * d.w);
+            const bool p = pred_at(m, a.H, a.W, a.thresh, g, y + d.top, x + d.left);
+            const bool t = ((gv >> (8 * j)) & 255u) != 0;
+            I += p && t; U += p || t;
+            pv |= (uint32_t)p << (8 * j);
+        }
+        if (mo) {
+            if (k == 4 && al_gt) *(uint32_t*)(mo + i4) = pv;
+            else for (int j = 0; j < k; ++j) mo[i4 + j] = (unsigned char)(pv >> (8 * j));
+        }
+    }
+    // wave sums, then one integer atomic per wave-partial per block
+    for (int off = 32; off > 0; off >>= 1) { I += __shfl_down(I, off, 64); U += __shfl_down(U, off, 64); }
+    __shared__ unsigned long long sI[NTHR / 64], sU[NTHR / 64];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sI[wave] = I; sU[wave] = U; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tI = 0, tU = 0;
+        for (int i = 0; i < NTHR / 64; ++i) { tI += sI[i]; tU += sU[i]; }
+        if (tI) atomicAdd(&a.iu[2 * b], tI);
+        if (tU) atomicAdd(&a.iu[2 * b + 1], tU);
+    }
+}
+
+// resize_and_pad_geometry / resize_and_crop_geometry (hostutil.py): Python's true division, np.round (half to even), int(floor(.) / 2)
+void geometry(int ih, int iw, int oh, int ow, bool pad, int out[4]) {
+    const double s = pad ? fmin((double)oh / ih, (double)ow / iw) : fmax((double)oh / ih, (double)ow / iw);
+    const int rh = (int)nearbyint(ih * s), rw = (int)nearbyint(iw * s);
+    out[0] = rh; out[1] = rw;
+    out[2] = (int)((double)(pad ? oh - rh : rh - oh) / 2.0);
+    out[3] = (int)((double)(pad ? ow - rw : rw - ow) / 2.0);
+}
+
+// skimage_like_resize's Gaussian and zoom constants for src -> dst
+bool sample_geo(int sh, int sw, int dh, int dw, SampleGeo& g) {
+    g.zy = (double)sh / dh; g.zx = (double)sw / dw;
+    g.sy = g.sx = 0.0; g.ry = g.rx = 0;
+    if (fmax(g.zy, g.zx) > 1.0) {
+        const double sy = fmax(0.0, (g.zy - 1.0) / 2.0), sx = fmax(0.0, (g.zx - 1.0) / 2.0);
+        if (sy > 1e-15) { g.sy = sy; g.ry = (int)(4.0 * sy + 0.5); }         // gaussian_filter skips sigma <= 1e-15
+        if (sx > 1e-15) { g.sx = sx; g.rx = (int)(4.0 * sx + 0.5); }
+    }
+    return g.ry <= MAXR && g.rx <= MAXR;
+}
+
+int check_descs(const char* who, const cmpc_eval_desc* ds, int B, int64_t bytes, int H, int W, bool pad, SampleGeo* geo) {
+    for (int b = 0; b < B; ++b) {
+        const cmpc_eval_desc& d = ds[b];
+        if (d.h <= 0 || d.w <= 0) { cmpc_set_error("%s: sample %d: empty or 1-D image (%d x %d)", who, b, d.h, d.w); return CMPC_EINVAL; }
+        if (pad ? (d.c != 1 && d.c != 3) : d.c != 1) { cmpc_set_error("%s: sample %d: %d channels", who, b, d.c); return CMPC_EINVAL; }
+        if (d.offset < 0 || d.offset > bytes || (int64_t)d.h * d.w * d.c > bytes - d.offset) {
+            cmpc_set_error("%s: sample %d: offset %lld + %lld bytes beyond the buffer (%lld)", who, b, (long long)d.offset,
+                           (long long)d.h * d.w * d.c, (long long)bytes);
+            return CMPC_EINVAL;
+        }
+        int gm[4];
+        if (pad) geometry(d.h, d.w, H, W, true, gm); else geometry(H, W, d.h, d.w, false, gm);
+        if (gm[0] != d.rh || gm[1] != d.rw || gm[2] != d.top || gm[3] != d.left || d.rh <= 0 || d.rw <= 0) {
+            cmpc_set_error("%s: sample %d: geometry (%d, %d, %d, %d) differs from resize_and_%s_geometry (%d, %d, %d, %d)", who, b, d.rh, d.rw,
+                           d.top, d.left, pad ? "pad" : "crop", gm[0], gm[1], gm[2], gm[3]);
+            return CMPC_EINVAL;
+        }
+        const bool ok = pad ? sample_geo(d.h, d.w, d.rh, d.rw, geo[b]) : sample_geo(H, W, d.rh, d.rw, geo[b]);
+        if (!ok) { cmpc_set_error("%s: sample %d: shrink factor too large (Gaussian radius > %d)", who, b, MAXR); return CMPC_EINVAL; }
+    }
+    return CMPC_OK;
+}
+
+constexpr size_t LDS_CAP = 64 * 1024 - 2 * (MAXR + 1) * sizeof(double);
+
+size_t prep_lds(const cmpc_eval_desc* ds, const SampleGeo* geo, int B, int ty, int tx) {
+    size_t m = 0;
+    for (int b = 0; b < B; ++b) {
+        int nyb, nyr, nxb, nxr;
+        tile_extent(geo[b].zy, ty, geo[b].ry, ds[b].h, nyb, nyr);
+        tile_extent(geo[b].zx, tx, geo[b].rx, ds[b].w, nxb, nxr);
+        const size_t c = ds[b].c;
+        m = std::max(m, (((size_t)nyr * nxr * c + 15) & ~(size_t)15) + (size_t)nyb * nxr * c * sizeof(double));
+    }
+    return m;
+}
+
+}  // namespace
+
+#define ST ((hipStream_t)stream)
+
+extern "C" int cmpc_eval_prep(const unsigned char* src, int64_t src_bytes, const cmpc_eval_desc* descs_host, int B, int H, int W,
+                              unsigned char* proc_im, float* feed, void* stream) {
+    if (!src || !descs_host || !proc_im || !feed) { cmpc_set_error("eval_prep: NULL pointer"); return CMPC_EINVAL; }
+    if (B <= 0 || B > CMPC_EVAL_MAX_BATCH) { cmpc_set_error("eval_prep: B = %d outside 1..%d", B, CMPC_EVAL_MAX_BATCH); return CMPC_EINVAL; }
+    if (H <= 0 || W <= 0 || src_bytes <= 0) { cmpc_set_error("eval_prep: bad output size %d x %d or buffer length", H, W); return CMPC_EINVAL; }
+    PrepArgs a;
+    const int rc = check_descs("eval_prep", descs_host, B, src_bytes, H, W, true, a.g);
+    if (rc) return rc;
+    // tile: 256 threads as ty x tx output pixels; shrink the tile until the staged footprint fits in 64 KB of LDS
+    static const int shapes[][2] = {{8, 32}, {4, 32}, {2, 32}, {1, 32}, {1, 16}, {1, 8}, {1, 4}, {1, 1}};
+    size_t lds = 0; int ty = 0, tx = 0;
+    for (auto& s : shapes) {
+        lds = prep_lds(descs_host, a.g, B, s[0], s[1]);
+        if (lds <= LDS_CAP) { ty = s[0]; tx = s[1]; break; }
+    }
+    if (!ty) { cmpc_set_error("eval_prep: source footprint does not fit in LDS"); return CMPC_EINVAL; }
+    a.src = src; a.src_bytes = src_bytes; a.proc = proc_im; a.feed = feed;
+    a.H = H; a.W = W; a.B = B; a.ty = ty; a.tx = tx;
+    a.tiles_x = (W + tx - 1) / tx;
+    a.tiles = a.tiles_x * ((H + ty - 1) / ty);
+    for (int b = 0; b < B; ++b) a.d[b] = descs_host[b];
+    const int per_sample = std::max(1, std::min(a.tiles, 2048 / B));        // memory-bound cap: ~2048 workgroups per launch
+    hipLaunchKernelGGL(eval_prep_kernel, dim3(per_sample, B), dim3(NTHR), lds, ST, a);
+    return cmpc_check_launch("eval_prep");
+}
+
+extern "C" int cmpc_eval_mask_iu(const void* map, int map_dt, int B, int H, int W, float thresh, const unsigned char* gt, int64_t gt_bytes,
+                                 const cmpc_eval_desc* descs_host, uint64_t* iu, unsigned char* mask_out, void* stream) {
+    if (!map || !gt || !descs_host || !iu) { cmpc_set_error("eval_mask_iu: NULL pointer"); return CMPC_EINVAL; }
+    if (map_dt != CMPC_EVAL_F32 && map_dt != CMPC_EVAL_U8) { cmpc_set_error("eval_mask_iu: map dtype %d is neither f32 nor u8", map_dt); return CMPC_EINVAL; }
+    if (B <= 0 || B > CMPC_EVAL_MAX_BATCH) { cmpc_set_error("eval_mask_iu: B = %d outside 1..%d", B, CMPC_EVAL_MAX_BATCH); return CMPC_EINVAL; }
+    if (H <= 0 || W <= 0 || gt_bytes <= 0) { cmpc_set_error("eval_mask_iu: bad map size %d x %d or buffer length", H, W); return CMPC_EINVAL; }
+    MaskArgs a;
+    const int rc = check_descs("eval_mask_iu", descs_host, B, gt_bytes, H, W, false, a.g);
+    if (rc) return rc;
+    a.map = map; a.map_dt = map_dt; a.H = H; a.W = W; a.B = B; a.thresh = thresh; a.gt = gt; a.mask_out = mask_out;
+    a.iu = (unsigned long long*)iu;
+    int64_t most = 0;
+    for (int b = 0; b < B; ++b) { a.d[b] = descs_host[b]; most = std::max(most, (int64_t)descs_host[b].h * descs_host[b].w); }
+    if (hipMemsetAsync(iu, 0, sizeof(uint64_t) * 2 * B, ST) != hipSuccess) { cmpc_set_error("eval_mask_iu: hipMemsetAsync"); return CMPC_EHIP; }
+    const int per_sample = (int)std::max<int64_t>(1, std::min<int64_t>((most + 4 * NTHR - 1) / (4 * NTHR), 2048 / B));
+    if (map_dt == CMPC_EVAL_F32) hipLaunchKernelGGL(eval_mask_iu_kernel<float>, dim3(per_sample, B), dim3(NTHR), 0, ST, a);
+    else hipLaunchKernelGGL(eval_mask_iu_kernel<unsigned char>, dim3(per_sample, B), dim3(NTHR), 0, ST, a);
+    return cmpc_check_launch("eval_mask_iu");
+}

@@ -145,3 +145,40 @@ class SegEval:
         out["overall_IoU"] = self.cum_I / self.cum_U
         out["mean_IoU"] = self.sum_iou / self.total
         return out
+
+
+def img_as_ubyte(x: np.ndarray) -> np.ndarray:
+    """skimage.img_as_ubyte of a float image as scikit-image >= 0.19 documents it: values must lie in [-1, 1]; x * 255 in float64,
+    rounded half to even, clipped to [0, 255] (negative values become 0).  Parity-unpinned like the resize restatement above."""
+    a = np.asarray(x)
+    if not np.issubdtype(a.dtype, np.floating):
+        raise ValueError("img_as_ubyte: expected a float image, got %s" % a.dtype)
+    if a.size and (np.min(a) < -1.0 or np.max(a) > 1.0):
+        raise ValueError("img_as_ubyte: images of type float must be between -1 and 1")
+    out = np.multiply(a, 255, dtype=np.float64)
+    np.rint(out, out=out)
+    np.clip(out, 0, 255, out=out)
+    return out.astype(np.uint8)
+
+
+def end_padded(text_front_padded, pad: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """The batches' `text_batch` (front-padded by preprocess_sentence, build_batches.py:70) -> the form CMPC_model is fed with
+    (test.py:267): END-padded int32 ids and int32 `seq_len`.  Accepts [T] or [B, T]; the leading run of `pad` ids is the padding.
+    An all-pad row (an empty sentence) raises ValueError: the text LSTM needs at least one word (seq_len >= 1)."""
+    a = np.asarray(text_front_padded)
+    if a.ndim not in (1, 2) or not np.issubdtype(a.dtype, np.integer) or a.shape[-1] == 0:
+        raise ValueError("end_padded: expected integer ids [T] or [B, T], got %s %s" % (a.dtype, a.shape))
+    rows = a.reshape(-1, a.shape[-1])
+    T = rows.shape[1]
+    ids = np.full(rows.shape, pad, dtype=np.int32)
+    seq_len = np.zeros(rows.shape[0], dtype=np.int32)
+    for i, r in enumerate(rows):
+        nz = np.flatnonzero(r != pad)
+        if nz.size == 0:
+            raise ValueError("end_padded: row %d holds only pad ids (empty sentence)" % i)
+        n = T - int(nz[0])
+        ids[i, :n] = r[nz[0]:]
+        seq_len[i] = n
+    if a.ndim == 1:
+        return ids[0], seq_len[0]
+    return ids, seq_len

@@ -1,0 +1,58 @@
+"""The reference's `-m test` loop (trainval_model.py:150-303) over the batches build_batches.py writes (<prefix>_<n>.npz with text_batch,
+im_batch, mask_batch, sent_batch; build_batches.py:72-76), on the GPU through evaluate.Evaluator.
+usage: python examples/evaluate_batches.py --folder DIR --prefix NAME --model CMPC_model --snapshot PATH [--batch 8] [--dcrf]
+       [--H 320 --W 320 --T 20]"""
+import argparse, glob, importlib, os, re, sys
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--folder", required=True)
+ap.add_argument("--prefix", required=True)
+ap.add_argument("--model", default="CMPC_model")
+ap.add_argument("--snapshot", required=True)
+ap.add_argument("--batch", type=int, default=8)
+ap.add_argument("--dcrf", action="store_true")
+ap.add_argument("--H", type=int, default=320)
+ap.add_argument("--W", type=int, default=320)
+ap.add_argument("--T", type=int, default=20)
+ap.add_argument("--model-kwargs", default="", help="extra model keywords, k=v comma-separated (e.g. a shrunken test graph)")
+args = ap.parse_args()
+
+pkg = importlib.import_module("cmpc-refseg_amd")
+CK = importlib.import_module("cmpc-refseg_amd.checkpoint")
+HU = importlib.import_module("cmpc-refseg_amd.hostutil")
+EV = importlib.import_module("cmpc-refseg_amd.evaluate")
+
+extra = {}
+for kv in filter(None, args.model_kwargs.split(",")):
+    k, v = kv.split("=")
+    extra[k] = tuple(int(x) for x in v.split(":")) if ":" in v else (v if not v.lstrip("-").isdigit() else int(v))
+model = pkg.get_segmentation_model(args.model, mode="eval", batch_size=args.batch, num_steps=args.T, H=args.H, W=args.W, **extra)
+CK.Saver().restore(model, args.snapshot)                       # test.py:252-264
+
+pat = re.compile(re.escape(args.prefix) + r"_(\d+)\.npz$")
+files = sorted((int(pat.search(f).group(1)), f) for f in glob.glob(os.path.join(args.folder, args.prefix + "_*.npz")) if pat.search(f))
+ev = EV.Evaluator(model, dcrf=args.dcrf)
+for _, f in files:
+    z = np.load(f)
+    ids, seq_len = HU.end_padded(z["text_batch"])
+    ev.add(ids, seq_len, z["im_batch"], z["mask_batch"])
+res = ev.result()
+
+
+def report(prefix):                                            # trainval_model.py:288-303
+    out = ""
+    for t in ev.thresholds:
+        out += "precision@%s = %f\n" % (str(t), res[prefix + "precision@%s" % t])
+    out += "overall IoU = %f; mean IoU = %f" % (res[prefix + "overall_IoU"], res[prefix + "mean_IoU"])
+    print(out)
+
+
+print("samples = %d" % res["samples"])
+report("")
+if args.dcrf:
+    print("DenseCRF:")
+    report("dcrf_")

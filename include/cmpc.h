@@ -507,6 +507,31 @@ int cmpc_launch_count(cmpc_handle h, int64_t* n);
 int cmpc_dense_crf(const float* sigm, const unsigned char* rgb, int H, int W, float sxy_g, float compat_g, float sxy_b, float srgb,
                    float compat_b, int iters, float* q_out, unsigned char* mask_out, void* stream);
 
+/* ---- Evaluation of a split (trainval_model.py:227-303, the `-m test` loop) at each sample's original size.  The resampler is
+ *      skimage.transform.resize as cmpc-refseg_amd/hostutil.py restates it (mirror Gaussian when shrinking, then ndimage.zoom order 1,
+ *      mode "mirror", grid_mode) -- parity-unpinned against scikit-image itself.  One descriptor per sample; descriptors are HOST
+ *      memory, validated before anything is launched and passed to the kernel by value.  B <= CMPC_EVAL_MAX_BATCH per call: larger
+ *      batches are split by the caller ------------------------------------------------------------------------------------------- */
+#define CMPC_EVAL_MAX_BATCH 32
+#define CMPC_EVAL_F32 0              /* map dtypes of cmpc_eval_mask_iu */
+#define CMPC_EVAL_U8 1
+typedef struct {
+    int64_t offset;                  /* byte offset of the sample in the packed uint8 buffer ([h, w, c] row-major) */
+    int h, w, c;                     /* c: 1 or 3 for cmpc_eval_prep, 1 for cmpc_eval_mask_iu */
+    int rh, rw, top, left;           /* resize_and_pad_geometry(h, w, H, W) / resize_and_crop_geometry(H, W, h, w) */
+    int pad_;
+} cmpc_eval_desc;
+/* proc_im [B, H, W, 3] uint8 = img_as_ubyte(resize_and_pad(im, H, W)) (a 1-channel image is tiled to 3, build_batches.py:67-68) and
+ * feed [B, H, W, 3] float32 = proc_im[..., ::-1].astype(float32) - mu, one float64 subtract rounded to float32 (trainval_model.py:227-230,371).
+ * src: packed uint8 images (src_bytes long).  The padding is written as 0 (proc_im) and -mu (feed). */
+int cmpc_eval_prep(const unsigned char* src, int64_t src_bytes, const cmpc_eval_desc* descs_host, int B, int H, int W,
+                   unsigned char* proc_im, float* feed, void* stream);
+/* iu [B][2] uint64 = (I, U) of compute_mask_IU(resize_and_crop(map >= thresh, h, w), gt) (trainval_model.py:244-245,267; eval_tools.py:31-35),
+ * exact integers.  map [B, H, W] float32 (up, thresh 1e-9) or uint8 (the DenseCRF argmax); gt: packed uint8 masks (non-zero = foreground,
+ * gt_bytes long).  mask_out: NULL, or a buffer laid out like gt that receives the predicted mask at the original size (uint8 {0, 1}). */
+int cmpc_eval_mask_iu(const void* map, int map_dt, int B, int H, int W, float thresh, const unsigned char* gt, int64_t gt_bytes,
+                      const cmpc_eval_desc* descs_host, uint64_t* iu, unsigned char* mask_out, void* stream);
+
 /* Host utility (no GPU): CRC-32C of `n` bytes, continuing from `crc` (0 to start) -- the checksum of TensorFlow's tensor-bundle
  * checkpoints (trainval_model.py:46-63 restores / saves them; cmpc-refseg_amd/tf_bundle.py reads and writes the format). */
 uint32_t cmpc_crc32c(uint32_t crc, const void* data, size_t n);
