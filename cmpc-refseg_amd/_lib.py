@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libcmpc_hip.so")
 
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
-MODEL_CMPC, MODEL_V5_BILSTM, MODEL_VIDEO = 0, 1, 2
+MODEL_CMPC, MODEL_V5_BILSTM, MODEL_VIDEO, MODEL_V5 = 0, 1, 2, 3
 ABI_VERSION = 3          # CMPC_ABI_VERSION of include/cmpc.h this binding was written against
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
 
@@ -192,6 +192,7 @@ SIGNATURES = {
     "cmpc_resize_bilinear_fwd": [_I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "cmpc_resize_bilinear_bwd": [_I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "cmpc_hsv_map": [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "cmpc_hsv_grid": [_I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "cmpc_reverse_sequence": [_P, _P, _P, _I, _I, _I, _P],
     "cmpc_reverse_words_tb": [_P, _P, _P, _I, _I, _P],
     "cmpc_rows_nonzero2": [_P, _P, _P, _I, _I, _I, _P],

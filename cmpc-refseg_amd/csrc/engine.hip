@@ -285,18 +285,23 @@ struct cmpc_engine_s {
     hipEvent_t user_bwd_levels = nullptr;     // caller's event, recorded when the levels' backward is complete (cmpc_set_bwd_levels_event)
     // buffers
     void* spatial = nullptr;
-    void* spatial1 = nullptr;        // the grid with a constant 1 in channel 8: A operand of the products whose row 8 is the bias gradient
-    bool mutan_bias_row = false;     // every vis_trans head's bias sits right behind its DW: its gradient is row C + 8 of the spatial-rows product
+    void* spatial1 = nullptr;        // the grid with a constant 1 in channel sp: A operand of the products whose row sp is the bias gradient
+    bool mutan_bias_row = false;     // every vis_trans head's bias sits right behind its DW: its gradient is row C + sp of the spatial-rows product
+    hipEvent_t ev_grid_read = nullptr;   // grid HSV: recorded once the last cmpc_backward's reads of the grid are enqueued (next grid write waits)
     float *wf, *wf_rstd, *mask;
     float *h1, *lg, *parse, *dlg, *dh1;
     float *vl, *vl_rstd, *nec, *nec_rstd, *dparse, *dwf, *dvl, *dnec;
-    // model variant (cfg.model): CMPC_model = 3 levels (c5, c4, c3), 3 exchange modules per round, 3 ConvLSTM steps; CMPCv5_BiLSTM = 2 / 2 / 2
+    // model variant (cfg.model): CMPC_model = 3 levels (c5, c4, c3), 3 exchange modules per round, 3 ConvLSTM steps; the v5 trunk = 2 / 2 / 2
     bool v5 = false; int nlev = 3, nex = 3, ncl = 3;
+    // properties of the graph that the v5 family varies (cmpc_create): CMPCv5_BiLSTM(_HSV) = BiLSTM encoder + tanh laterals + tanh gv_lang +
+    // HSV on the c5 / c4 taps; CMPCv5(_HSV) = CMPC_model's encoder, no tanh, HSV in the spatial grid
+    bool bilstm = false, lat_tanh = false, gv_tanh = false, hsv_taps = false, hsv_grid = false;
+    int sp = 8;                      // valid channels of the spatial grid: 8 (util/processing_tools.py:5-17), 11 with grid HSV (CMPCv5_HSV_model.py:136-144)
     bool vid = false; int Fr = 1, RF = 0, NC = 4;      // model VIDEO: sampled frames, rows of the per-frame maps (Fr * N, batch 1); parser classes (4 or 5)
     float *ac = nullptr, *ac_rstd = nullptr, *dac = nullptr, *ea_t = nullptr, *ones_t = nullptr, *zeros_nt = nullptr;
     LstmDir ldir[2]; int ndir = 1;
     float *outs_bw = nullptr, *douts_bw = nullptr, *wft = nullptr, *dwft = nullptr;     // v5: un-reversed backward outputs / their gradient; tanh(words_feat conv)
-    void* hsv = nullptr;                                               // v5 hsv: [R, 64] map (3 channels)
+    void* hsv = nullptr;                                               // hsv_taps: [R, 64] map (3 channels)
     // v5: ASPP + decoder (CMPCv5_BiLSTM_model.py:190-251)
     int D = 0, Dp = 0, LOW = 0, CATp = 0, C2 = 0, h2 = 0, w2 = 0, R2 = 0;
     BnLayer bn[9];                  // aspp 1x1, 3x3 x3, image level, concat; decoder low level, 3x3 x2  (bn_scopes order)
@@ -312,6 +317,7 @@ struct cmpc_engine_s {
     float* scalars; int* nonfinite;      // nonfinite[b]: gradient elements of bucket b the last optimizer step skipped (inf / nan)
     bool have_target = false;
     bool bwd_zeroed = false;      // the backward pass's accumulate-into buffers and the gradient buffer were cleared by the last cmpc_forward
+    bool grads_pending = false;   // a cmpc_backward wrote gradients that no optimizer step (its last bucket) has consumed yet
     const int32_t* seq_len_feed = nullptr; const float* target_feed = nullptr;      // caller-owned feeds the backward pass re-reads
     hipStream_t last_main = nullptr; long l0 = 0;
     // Gradient buckets: contiguous ranges of the flat gradient buffer in the order they become final during cmpc_backward
@@ -386,12 +392,12 @@ void add_ln(E* e, const std::string& scope, int dim) {
 }
 void build_manifest(E* e) {
     const int C = e->C, M = e->M, R = e->RNN;
-    const int hx = (e->v5 && e->cfg.hsv) ? 3 : 0;
+    const int hx = e->hsv_taps ? 3 : 0, sp = e->sp;
     add_param(e, "Variable", {e->V, e->G}, 0.f, 1.f);
     if (e->vid) {                                                                  // vid:105-133: MultiRNNCell([BasicLSTMCell]) under scope "RNN"
         add_param(e, "RNN/multi_rnn_cell/cell_0/basic_lstm_cell/kernel", {e->G + R, 4 * R}, 0.f, 1.f);
         add_param(e, "RNN/multi_rnn_cell/cell_0/basic_lstm_cell/bias", {4 * R}, 0.f, 1.f);
-    } else if (!e->v5) {
+    } else if (!e->bilstm) {                                                       // lstm(): CMPC_model.py:144-164, CMPCv5_model.py:158-178
         add_param(e, "rnn/lstm_cell/kernel", {e->G + R, 4 * R}, 0.f, 1.f);
         add_param(e, "rnn/lstm_cell/bias", {4 * R}, 0.f, 1.f);
     } else {                                                                       // BiLSTM(), v5:159-187
@@ -409,7 +415,7 @@ void build_manifest(E* e) {
     for (int li = 0; li < e->nlev; ++li) {
         const char* lv = lvn(e, li);
         for (int hd = 1; hd <= 5; ++hd) {
-            add_conv(e, fmt("vis_trans_%s_head%d", lv, hd), 1, C + 8, C);
+            add_conv(e, fmt("vis_trans_%s_head%d", lv, hd), 1, C + sp, C);      // CMPCv5_HSV_model.py:390-392: C + 8 + 3
             add_conv(e, fmt("lang_trans_%s_head%d", lv, hd), 1, R, C);
         }
         if (e->vid) {                                                              // build_temp_graph / build_temp_ctx, vid:458-530
@@ -428,7 +434,7 @@ void build_manifest(E* e) {
         add_ln(e, fmt("gconv_feat_ln_spa_graph_%s", lv), C);
         add_conv(e, fmt("gconv_update_spa_graph_%s", lv), 1, C, C);
         add_ln(e, fmt("gconv_update_ln_spa_graph_%s", lv), C);
-        add_conv(e, fmt("fusion_%s", lv), 1, (e->vid ? 3 : 2) * C + R + 8, M);        // vid:398-400: [lateral | spatial graph | temporal context | lang | grid]
+        add_conv(e, fmt("fusion_%s", lv), 1, (e->vid ? 3 : 2) * C + R + sp, M);       // vid:398-400: [lateral | spatial graph | temporal context | lang | grid]
     }
     for (int li = 0; li < e->nlev; ++li) add_conv(e, fmt("score_%s", lvn(e, li)), 3, M, 1);
     for (int xi = 0; xi < 2 * e->nex; ++xi) {
@@ -531,7 +537,7 @@ void plan_operands(E* e) {
         linear(e, D.key, D.pk, L, G + R, 4 * R, Gp + Cp, 4 * Cp, true, true, {{0, G, 0}, {G, R, Gp}}, gate_ns);
         Operand& ob = new_operand(e, D.key + ".b", L, 1, 4 * Cp); add_desc(e, ob, D.pb, 4 * R, 0, 0, 0, 1, 4 * Cp, {{0, 1, 0}}, gate_ns);
     }
-    if (e->v5) linear(e, "wfeat", "words_feat/DW", L, 2 * R, R, 2 * Cp, Cp, true, true, {{0, R, 0}, {R, R, Cp}});      // [fw | bw] -> R (v5:182)
+    if (e->bilstm) linear(e, "wfeat", "words_feat/DW", L, 2 * R, R, 2 * Cp, Cp, true, true, {{0, R, 0}, {R, R, Cp}});      // [fw | bw] -> R (v5:182)
     linear(e, "parse1", "words_parse_1/DW", L, R, P, Cp, Pp);
     linear(e, "parse2", "words_parse_2/DW", L, P, e->NC, Pp, 64);
     e->stage0_ndesc = (int)e->descs.size();       // what the text encoder + parser read: packed (and published) first
@@ -539,13 +545,13 @@ void plan_operands(E* e) {
     for (int i = 0; i < e->nlev; ++i) {
         // hsv: the three HSV channels are a K-segment of their own (rows cin .. cin+2 of the weight -> k = pad64(cin) ..), read from e->hsv
         Segs ks = {{0, cins[i], 0}};
-        const bool hx = e->v5 && e->cfg.hsv;
+        const bool hx = e->hsv_taps;
         if (hx) ks.push_back({cins[i], 3, pad64(cins[i])});
         linear(e, fmt("lat_%s", lvn(e, i)), fmt("%s_lateral/DW", lvn(e, i)), V, cins[i] + (hx ? 3 : 0), C, pad64(cins[i]) + (hx ? 64 : 0), Cp, true, e->cfg.conv5 != 0, ks);
     }
     for (int li = 0; li < e->nlev; ++li) {
         const char* lv = lvn(e, li);
-        // mutan: five heads side by side; forward operand [5Cp][Cp+64] (k: C visual rows, then the 8 spatial rows)
+        // mutan: five heads side by side; forward operand [5Cp][Cp+64] (k: C visual rows, then the sp = 8 or 11 grid rows)
         Operand opt = new_operand(e, fmt("mutan_%s.t", lv), V, 5 * Cp, Cp + 64);
         Operand opn = new_operand(e, fmt("mutan_%s.n", lv), V, Cp, 5 * Cp);
         Operand lgt = new_operand(e, fmt("mlang_%s.t", lv), L, 5 * Cp, Cp);
@@ -554,7 +560,7 @@ void plan_operands(E* e) {
         Operand lgb = new_operand(e, fmt("mlang_%s.b", lv), L, 1, 5 * Cp);
         for (int hd = 0; hd < 5; ++hd) {
             const std::string pn = fmt("vis_trans_%s_head%d/DW", lv, hd + 1), pl = fmt("lang_trans_%s_head%d/DW", lv, hd + 1);
-            add_desc(e, opt, pn, C, 1, hd * Cp, 0, Cp, Cp + 64, {{0, C, 0}, {C, 8, Cp}}, {{0, C, 0}});
+            add_desc(e, opt, pn, C, 1, hd * Cp, 0, Cp, Cp + 64, {{0, C, 0}, {C, e->sp, Cp}}, {{0, C, 0}});
             add_desc(e, opn, pn, C, 0, 0, hd * Cp, Cp, Cp, {{0, C, 0}}, {{0, C, 0}});
             add_desc(e, lgt, pl, C, 1, hd * Cp, 0, Cp, Cp, {{0, R, 0}}, {{0, C, 0}});
             add_desc(e, lgn, pl, C, 0, 0, hd * Cp, Cp, Cp, {{0, R, 0}}, {{0, C, 0}});
@@ -566,7 +572,7 @@ void plan_operands(E* e) {
         linear(e, fmt("gupd_%s", lv), fmt("gconv_update_spa_graph_%s/DW", lv), V, C, C, Cp, Cp);
         const std::string fus = fmt("fusion_%s/DW", lv);
         if (!e->vid) {
-            linear(e, fmt("fus_%s", lv), fus, V, 2 * C + R + 8, M, 2 * Cp + 64, Mp, true, true, {{0, C, 0}, {C, C, Cp}, {2 * C + R, 8, 2 * Cp}});
+            linear(e, fmt("fus_%s", lv), fus, V, 2 * C + R + e->sp, M, 2 * Cp + 64, Mp, true, true, {{0, C, 0}, {C, C, Cp}, {2 * C + R, e->sp, 2 * Cp}});
             linear(e, fmt("fusl_%s", lv), fus, L, R, M, Cp, Mp, true, true, {{2 * C, R, 0}});
         } else {
             // three visual K-segments; the tiled language vector is a per-sample bias and the grid a per-position bias (both float32 products)
@@ -688,13 +694,12 @@ void plan_workspace(E* e, Bump& zf, Bump& zb, Bump& g) {
         D.sync_f = (int*)zf.take(256); D.sync_b = (int*)zb.take(256);
         tap(e, fmt("lstm_sync_%d", d), D.sync_f, 3, {2}); tap(e, fmt("lstm_sync_bwd_%d", d), D.sync_b, 3, {2});
     }
-    if (e->v5) {
+    if (e->bilstm) {
         e->outs_bw = (float*)g.take((size_t)B * T * Cp * F); e->douts_bw = (float*)g.take((size_t)B * T * Cp * F);
         e->wft = (float*)g.take((size_t)B * T * Cp * F); e->dwft = (float*)g.take((size_t)B * T * Cp * F);
-        if (e->cfg.hsv) e->hsv = g.take((size_t)R * 64 * es);
         tap(e, "bilstm_fw", e->ldir[0].outs, 0, {B * T, Cp}); tap(e, "bilstm_bw", e->outs_bw, 0, {B * T, Cp});
-        if (e->cfg.hsv) tap(e, "hsv", e->hsv, vd, {R, 64});
     }
+    if (e->hsv_taps) { e->hsv = g.take((size_t)R * 64 * es); tap(e, "hsv", e->hsv, vd, {R, 64}); }
     e->wf = (float*)g.take((size_t)B * T * Cp * F);
     e->wf_rstd = (float*)g.take((size_t)B * T * F);
     e->mask = (float*)g.take((size_t)B * T * F);
@@ -725,7 +730,7 @@ void plan_workspace(E* e, Bump& zf, Bump& zb, Bump& g) {
         LevelBuf& L = e->lv[i]; const char* n = lvn(e, i);
         L.cin = cins[i];
         L.X0 = g.take((size_t)RL * Cp * es); L.lat_rstd = (float*)g.take((size_t)RL * F);
-        L.X0t = e->v5 ? g.take((size_t)R * Cp * es) : nullptr;
+        L.X0t = e->lat_tanh ? g.take((size_t)R * Cp * es) : nullptr;
         L.g = (float*)g.take((size_t)BL * 5 * Cp * F); L.P = g.take((size_t)RL * 5 * Cp * es);
         L.X1 = g.take((size_t)RL * Cp * es); L.mut_rstd = (float*)g.take((size_t)RL * F);
         L.Wd = (float*)zf.take((size_t)B * Tp * Cp * F);
@@ -942,7 +947,7 @@ int gemm_nt(hipStream_t st, int dt, std::initializer_list<Seg> segs, void* C, in
         (void)hipEventRecord(e1, st);
         te->timing = true;
         double kalg = 0;
-        for (const Seg& s : segs) kalg += (s.A == te->spatial && s.K == 64) ? 8 : valid_extent(te, s.K);
+        for (const Seg& s : segs) kalg += (s.A == te->spatial && s.K == 64) ? te->sp : valid_extent(te, s.K);
         const double nv = valid_extent(te, o.n_valid < 0 ? N : o.n_valid), rows = (double)M * o.batch;
         te->tev.push_back(e0); te->tev.push_back(e1);
         { int kp = 0; for (const Seg& s : segs) kp += s.K; te->tshape.push_back({M * o.batch, N, kp, (int)segs.size()}); }
@@ -1105,13 +1110,14 @@ int lstm_dir_bwd(E* e, hipStream_t st, LstmDir& D, const int32_t* seq_len) {
     return CMPC_OK;
 }
 
-// lstm(), CMPC_model.py:144-164 -- or BiLSTM(), CMPCv5_BiLSTM_model.py:159-187 (the backward direction on lane 1 beside the forward one)
+// lstm(), CMPC_model.py:144-164 (CMPCv5_model.py:158-178 is the same) -- or BiLSTM(), CMPCv5_BiLSTM_model.py:159-187 (the backward
+// direction on lane 1 beside the forward one)
 int text_fwd(E* e, hipStream_t st, const int32_t* words, const int32_t* seq_len) {
     const int B = e->B, T = e->T, R = e->RNN, Cp = e->Cp;
     LstmDir& F = e->ldir[0];
     hipLaunchKernelGGL(transpose_i32_kernel, dim3((B * T + 255) / 256), dim3(256), 0, st, words, F.words_tb, B, T);
     CK(cmpc_check_launch("transpose_i32"));
-    if (!e->v5) {
+    if (!e->bilstm) {
         CK(lstm_dir_fwd(e, st, F, seq_len));
         return cmpc_l2norm_rows_fwd(DT_F32, F.outs, e->wf, e->wf_rstd, e->mask, B * T, Cp, R, st);
     }
@@ -1139,7 +1145,7 @@ int text_fwd(E* e, hipStream_t st, const int32_t* words, const int32_t* seq_len)
 int text_bwd(E* e, hipStream_t st, const int32_t* seq_len) {
     const int B = e->B, T = e->T, R = e->RNN, G = e->G, Cp = e->Cp, Gp = e->Gp;
     LstmDir& F = e->ldir[0];
-    if (!e->v5) {
+    if (!e->bilstm) {
         CK(cmpc_l2norm_rows_bwd(DT_F32, e->dwf, e->wf, e->wf_rstd, F.douts, B * T, Cp, R, 0, st));
         CK(lstm_dir_bwd(e, st, F, seq_len));
         return cmpc_embed_scatter(F.demb, Gp, F.words_tb, gptr(e, "Variable"), T * B, G, e->V, st);
@@ -1231,15 +1237,16 @@ int level_lang_fwd(E* e, hipStream_t st, int li) {
 int level_fwd(E* e, hipStream_t st, int li, const float* target) {
     LevelBuf& L = e->lv[li]; const char* lv = lvn(e, li);
     const int B = e->B, N = e->N, T = e->T, R = e->R, C = e->C, Cp = e->Cp, Tp = e->Tp, M = e->M, Mp = e->Mp, dt = e->dt;
-    // -- lateral 1x1 conv + l2_normalize (CMPC_model.py:108-113); CMPCv5_BiLSTM: tanh in between (v5:120-125), HSV channels as a K-segment (hsv:128-134)
-    if (!e->v5) {
+    // -- lateral 1x1 conv + l2_normalize (CMPC_model.py:108-113, CMPCv5_model.py:119-122); CMPCv5_BiLSTM: tanh in between (v5:120-125), HSV
+    //    channels as a K-segment (hsv:128-134)
+    if (!e->lat_tanh) {
       GemmOpt o; o.n_valid = C; o.bias = pptr(e, fmt("%s_lateral/biases", lv));
       CK(gemm_nt(st, dt, {{L.feat, L.cin, opp(e, fmt("lat_%s.t", lv)), L.cin, L.cin}}, L.X0, Cp, R, Cp, o));
       CK(cmpc_l2norm_rows_fwd(dt, L.X0, L.X0, L.lat_rstd, nullptr, R, Cp, C, st));
     } else {
       GemmOpt o; o.n_valid = C; o.bias = pptr(e, fmt("%s_lateral/biases", lv)); o.act = ACT_TANH;
       const std::string k = fmt("lat_%s.t", lv);
-      if (e->cfg.hsv) {
+      if (e->hsv_taps) {
           const int ldk = L.cin + 64;
           CK(gemm_nt(st, dt, {{L.feat, L.cin, opp(e, k), ldk, L.cin}, {e->hsv, 64, opp(e, k, 0, L.cin), ldk, 64}}, L.X0t, Cp, R, Cp, o));
       } else CK(gemm_nt(st, dt, {{L.feat, L.cin, opp(e, k), L.cin, L.cin}}, L.X0t, Cp, R, Cp, o));
@@ -1299,7 +1306,7 @@ int level_bwd(E* e, hipStream_t st, int li, const float* target) {
       float* gw = gptr(e, fmt("fusion_%s/DW", lv));
       CK(gemm_tn(e, st, dt, L.X1, Cp, Cp, L.dpre, Mp, Mp, gw, M, R, C, M, OFF0, d));
       CK(gemm_tn(e, st, dt, L.X2, Cp, Cp, L.dpre, Mp, Mp, gw + (size_t)C * M, M, R, C, M, OFF0, d));
-      CK(gemm_tn(e, st, dt, e->spatial, 64, 64, L.dpre, Mp, Mp, gw + (size_t)(2 * C + Rr) * M, M, R, 8, M, OFF0, d));
+      CK(gemm_tn(e, st, dt, e->spatial, 64, 64, L.dpre, Mp, Mp, gw + (size_t)(2 * C + Rr) * M, M, R, e->sp, M, OFF0, d));
       CK(gemm_tn(e, st, DT_F32, e->vl, Cp, Cp, L.dsb, Mp, Mp, gw + (size_t)2 * C * M, M, B, Rr, M, OFF0, d));
       const std::string k = fmt("fus_%s.n", lv);
       GemmOpt o; o.n_valid = C;
@@ -1369,10 +1376,10 @@ int level_bwd(E* e, hipStream_t st, int li, const float* target) {
       }
       float* gwv = gptr(e, fmt("vis_trans_%s_head1/DW", lv));
       CK(gemm_tn(e, st, dt, L.X0, Cp, Cp, dP, 5 * Cp, Cp, gwv, C, R, C, C, ov, d));
-      // the grid rows of the five heads' DW; with the constant-1 channel the product's ninth row is the head's bias gradient (five column-sum
+      // the grid rows of the five heads' DW; with the constant-1 channel the product's row sp is the head's bias gradient (five column-sum
       // passes over dP = 130 MB per level less)
-      if (e->mutan_bias_row) CK(gemm_tn(e, st, dt, e->spatial1, 64, 64, dP, 5 * Cp, Cp, gwv, C, R, 9, C, os, d));
-      else CK(gemm_tn(e, st, dt, e->spatial, 64, 64, dP, 5 * Cp, Cp, gwv, C, R, 8, C, os, d));
+      if (e->mutan_bias_row) CK(gemm_tn(e, st, dt, e->spatial1, 64, 64, dP, 5 * Cp, Cp, gwv, C, R, e->sp + 1, C, os, d));
+      else CK(gemm_tn(e, st, dt, e->spatial, 64, 64, dP, 5 * Cp, Cp, gwv, C, R, e->sp, C, os, d));
       GemmOpt o; o.n_valid = C;
       CK(gemm_nt(st, dt, {{dP, 5 * Cp, opp(e, fmt("mutan_%s.n", lv)), 5 * Cp, 5 * Cp}}, L.dX0, Cp, R, Cp, o));
       const int64_t base_l = poff(e, fmt("lang_trans_%s_head1/DW", lv));
@@ -1387,14 +1394,14 @@ int level_bwd(E* e, hipStream_t st, int li, const float* target) {
       CK(gemm_nt(st, DT_F32, {{L.dg, 5 * Cp, opp(e, fmt("mlang_%s.n", lv)), 5 * Cp, 5 * Cp}}, L.dvl, Cp, B, Cp, v)); }
     // -- lateral
     CK(cmpc_l2norm_rows_bwd(dt, L.dX0, L.X0, L.lat_rstd, L.dV, R, Cp, C, 0, st));
-    if (!e->v5) CK(colsum(st, dt, L.dV, R, Cp, Cp, C, gptr(e, fmt("%s_lateral/biases", lv))));
+    if (!e->lat_tanh) CK(colsum(st, dt, L.dV, R, Cp, Cp, C, gptr(e, fmt("%s_lateral/biases", lv))));
     else CK(colsum(st, dt, L.dV, R, Cp, Cp, C, gptr(e, fmt("%s_lateral/biases", lv)), L.X0t, L.dV, ACT_TANH));
     float* glw = gptr(e, fmt("%s_lateral/DW", lv));
     if (e->cfg.conv5) {      // conv5=True: the tap's own gradient, for the caller's backbone backward (CMPC_model.py:427-430)
         GemmOpt o; o.n_valid = L.cin;
         CK(gemm_nt(st, dt, {{L.dV, Cp, opp(e, fmt("lat_%s.n", lv)), Cp, Cp}}, L.dfeat, L.cin, R, L.cin, o));
     }
-    if (e->v5 && e->cfg.hsv) CK(gemm_tn(e, st, dt, e->hsv, 64, 64, L.dV, Cp, Cp, glw + (size_t)L.cin * C, C, R, 3, C, OFF0, d));
+    if (e->hsv_taps) CK(gemm_tn(e, st, dt, e->hsv, 64, 64, L.dV, Cp, Cp, glw + (size_t)L.cin * C, C, R, 3, C, OFF0, d));
     return gemm_tn(e, st, dt, L.feat, L.cin, L.cin, L.dV, Cp, Cp, glw, C, R, L.cin, C, OFF0, d);
 }
 
@@ -1686,7 +1693,8 @@ int exchange_lang_fwd(E* e, hipStream_t st, int xi) {
     GemmOpt k; k.n_valid = M;
     return gemm_nt(st, DT_F32, {{X.q, Mp, opp(e, fmt("key_%s.n", lv)), Mp, Mp}}, X.kq, Mp, B, Mp, k);
 }
-// f2 == nullptr: one gated branch (CMPCv5_BiLSTM_model.py:343-346), and tanh before the all-dims l2_normalize of gv_lang (v5:328-329)
+// f2 == nullptr: one gated branch (CMPCv5_BiLSTM_model.py:343-346); gv_tanh: tanh before the all-dims l2_normalize of gv_lang (v5:328-329,
+// not in CMPCv5_model.py:318)
 int exchange_fwd(E* e, hipStream_t st, int xi, const void* feat, const void* f1, const void* f2) {
     ExgBuf& X = e->ex[xi]; const char* lv = exn(e, xi);
     const int B = e->B, N = e->N, R = e->R, Cp = e->Cp, M = e->M, Mp = e->Mp, dt = e->dt;
@@ -1696,7 +1704,7 @@ int exchange_fwd(E* e, hipStream_t st, int xi, const void* feat, const void* f1,
     CK(cmpc_softmax_n_fwd(X.logits, X.attn, B, N, st));
     CK(cmpc_wcolsum(dt, feat, X.attn, X.pooled, Mp, B, N, Mp, M, 1.0f, st));
     const int ldk = Mp + Cp; const std::string gvk = fmt("gv_%s.t", lv);
-    GemmOpt g; g.n_valid = M; g.bias = pptr(e, fmt("gv_lang_%sgv_f1/biases", lv)); if (e->v5) g.act = ACT_TANH;
+    GemmOpt g; g.n_valid = M; g.bias = pptr(e, fmt("gv_lang_%sgv_f1/biases", lv)); if (e->gv_tanh) g.act = ACT_TANH;
     CK(gemm_nt(st, DT_F32, {{X.pooled, Mp, opp(e, gvk), ldk, Mp}, {e->nec, Cp, opp(e, gvk, 0, Mp), ldk, Cp}}, X.gvpre, Mp, B, Mp, g));
     CK(cmpc_l2norm_all_fwd(X.gvpre, X.gv, X.rs1, B * Mp, st));
     const void* fx[2] = {f1, f2}; const char* fn[2] = {"f1", "f2"};
@@ -1735,7 +1743,7 @@ int exchange_bwd(E* e, hipStream_t st, int xi, const void* dout, const void* fea
         CK(gemm_nt(st, DT_F32, {{X.dg[i], Mp, opp(e, fmt("lfeat_%s_%s.n", lv, fn[i])), Mp, Mp}}, X.dgv, Mp, B, Mp, a));
     }
     CK(cmpc_l2norm_all_bwd(X.dgv, X.gv, X.rs1, X.dgvpre, B * Mp, st));
-    if (!e->v5) CK(colsum(st, DT_F32, X.dgvpre, B, Mp, Mp, M, gptr(e, fmt("gv_lang_%sgv_f1/biases", lv))));
+    if (!e->gv_tanh) CK(colsum(st, DT_F32, X.dgvpre, B, Mp, Mp, M, gptr(e, fmt("gv_lang_%sgv_f1/biases", lv))));
     else CK(colsum(st, DT_F32, X.dgvpre, B, Mp, Mp, M, gptr(e, fmt("gv_lang_%sgv_f1/biases", lv)), X.gvpre, X.dgvpre, ACT_TANH));     // X.gvpre holds tanh(...)
     float* gwg = gptr(e, fmt("gv_lang_%sgv_f1/DW", lv));
     CK(gemm_tn(e, st, DT_F32, X.pooled, Mp, Mp, X.dgvpre, Mp, Mp, gwg, M, B, M, M, OFF0, d));
@@ -2018,13 +2026,16 @@ extern "C" int cmpc_default_cfg(cmpc_cfg* c) {
 }
 // the caller's graph-shaping fields (batch_size, num_steps, vf_h, vf_w, H, W, ...) are kept; only the model-specific ones are set
 extern "C" int cmpc_default_cfg_model(cmpc_cfg* c, int model, int hsv) {
-    if (!c || (model != CMPC_MODEL_CMPC && model != CMPC_MODEL_V5_BILSTM && model != CMPC_MODEL_VIDEO)) { cmpc_set_error("default_cfg_model: bad argument"); return CMPC_EINVAL; }
+    if (!c || (model != CMPC_MODEL_CMPC && model != CMPC_MODEL_V5_BILSTM && model != CMPC_MODEL_VIDEO && model != CMPC_MODEL_V5)) {
+        cmpc_set_error("default_cfg_model: bad argument"); return CMPC_EINVAL;
+    }
+    const bool v5 = model == CMPC_MODEL_V5_BILSTM || model == CMPC_MODEL_V5;
     c->sample_frames = 5;                             // CMPC_video_mm_tgraph_allvec.py:69
     c->conv5 = 0; c->freeze_bn = 0;
-    c->model = model; c->hsv = (model == CMPC_MODEL_V5_BILSTM && hsv) ? 1 : 0;
+    c->model = model; c->hsv = (v5 && hsv) ? 1 : 0;
     c->bn_decay = 0.9997f; c->c2_dim = 256; c->c2_h = c->H / 4; c->c2_w = c->W / 4; c->aspp_depth = 256; c->low_dim = 48;
     c->aspp_rates[0] = 6; c->aspp_rates[1] = 12; c->aspp_rates[2] = 18;
-    if (model == CMPC_MODEL_V5_BILSTM) { c->loss_w[0] = 0.8f; c->loss_w[1] = 0.1f; c->loss_w[2] = 0.1f; c->loss_w[3] = 0.f; c->bn_train = 1; }     // v5:541-542
+    if (v5) { c->loss_w[0] = 0.8f; c->loss_w[1] = 0.1f; c->loss_w[2] = 0.1f; c->loss_w[3] = 0.f; c->bn_train = 1; }     // v5:541-542 (CMPCv5_model.py: the same)
     else { c->loss_w[0] = 0.7f; c->loss_w[1] = c->loss_w[2] = c->loss_w[3] = 0.1f; c->bn_train = 0; }
     return CMPC_OK;
 }
@@ -2041,6 +2052,7 @@ extern "C" int cmpc_destroy(cmpc_handle e) {
     for (hipEvent_t ev : e->evpool) (void)hipEventDestroy(ev);
     if (e->ev_opt0) (void)hipEventDestroy(e->ev_opt0);
     if (e->ev_opt1) (void)hipEventDestroy(e->ev_opt1);
+    if (e->ev_grid_read) (void)hipEventDestroy(e->ev_grid_read);
     for (hipEvent_t ev : e->bucket_ev) if (ev) (void)hipEventDestroy(ev);
     delete e;
     return CMPC_OK;
@@ -2061,17 +2073,18 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
     }
     if (pad64(c->v_emb_dim) > 2048 || pad64(c->mlp_dim) > 2048) { cmpc_set_error("create: v_emb_dim, mlp_dim <= 2048 (per-column registers of the map kernels)"); return CMPC_EINVAL; }
     if (c->n_lanes < 1 || c->n_lanes > 3) { cmpc_set_error("create: n_lanes must be 1, 2 or 3"); return CMPC_EINVAL; }
-    if (c->model != CMPC_MODEL_CMPC && c->model != CMPC_MODEL_V5_BILSTM && c->model != CMPC_MODEL_VIDEO) {
-        cmpc_set_error("create: model must be CMPC_MODEL_CMPC (0), CMPC_MODEL_V5_BILSTM (1) or CMPC_MODEL_VIDEO (2)"); return CMPC_EINVAL;
+    if (c->model != CMPC_MODEL_CMPC && c->model != CMPC_MODEL_V5_BILSTM && c->model != CMPC_MODEL_VIDEO && c->model != CMPC_MODEL_V5) {
+        cmpc_set_error("create: model must be CMPC_MODEL_CMPC (0), CMPC_MODEL_V5_BILSTM (1), CMPC_MODEL_VIDEO (2) or CMPC_MODEL_V5 (3)"); return CMPC_EINVAL;
     }
+    if (c->model == CMPC_MODEL_V5 && c->hsv != 0 && c->hsv != 1) { cmpc_set_error("create (CMPCv5): hsv must be 0 (CMPCv5_model) or 1 (CMPCv5_HSV_model)"); return CMPC_EINVAL; }
     if (c->model == CMPC_MODEL_VIDEO && (c->batch_size != 1 || c->sample_frames < 1 || c->sample_frames > 8)) {
         cmpc_set_error("create (CMPC_video): the graph is only valid for batch_size = 1 (CMPC_video_mm_tgraph_allvec.py:323-324,379); 1 <= sample_frames <= 8"); return CMPC_EINVAL;
     }
-    if (c->model == CMPC_MODEL_V5_BILSTM) {
+    if (c->model == CMPC_MODEL_V5_BILSTM || c->model == CMPC_MODEL_V5) {
         if (c->c2_dim < 64 || c->c2_dim % 64 || c->c2_h < c->vf_h || c->c2_w < c->vf_w || c->aspp_depth < 8 || c->aspp_depth % 4 || pad64(c->aspp_depth) > 512 ||
             c->low_dim < 4 || c->low_dim % 4 || c->low_dim > 64 || c->aspp_rates[0] < 1 || c->aspp_rates[1] < 1 || c->aspp_rates[2] < 1 || c->mlp_dim % 4 ||
             !(c->bn_decay >= 0.f && c->bn_decay <= 1.f)) {
-            cmpc_set_error("create (CMPCv5_BiLSTM): need c2_dim a multiple of 64, c2_h >= vf_h, c2_w >= vf_w, aspp_depth a multiple of 4 with pad64 <= 512, "
+            cmpc_set_error("create (CMPCv5 trunk): need c2_dim a multiple of 64, c2_h >= vf_h, c2_w >= vf_w, aspp_depth a multiple of 4 with pad64 <= 512, "
                            "low_dim a multiple of 4 and <= 64, rates >= 1, mlp_dim a multiple of 4, 0 <= bn_decay <= 1"); return CMPC_EINVAL;
         }
     }
@@ -2100,12 +2113,19 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
     e->H = c->H; e->W = c->W; e->V = c->vocab_size;
     e->C = c->v_emb_dim; e->Cp = pad64(e->C); e->M = c->mlp_dim; e->Mp = pad64(e->M); e->G = c->glove_dim; e->Gp = pad64(e->G);
     e->P = c->parse_dim; e->Pp = pad64(e->P); e->Tp = 64; e->RNN = c->rnn_size; e->dt = c->dtype; e->esz = c->dtype == DT_F32 ? 4 : 2;
-    e->v5 = c->model == CMPC_MODEL_V5_BILSTM;
+    e->v5 = c->model == CMPC_MODEL_V5_BILSTM || c->model == CMPC_MODEL_V5;
+    e->bilstm = e->lat_tanh = e->gv_tanh = c->model == CMPC_MODEL_V5_BILSTM;
+    e->hsv_taps = c->model == CMPC_MODEL_V5_BILSTM && c->hsv;
+    e->hsv_grid = c->model == CMPC_MODEL_V5 && c->hsv;
+    e->sp = e->hsv_grid ? 11 : 8;
     e->vid = c->model == CMPC_MODEL_VIDEO;
     if (e->vid) { e->Fr = c->sample_frames; e->RF = e->Fr * e->N; e->NC = 5; }
     if (e->v5) {
-        e->nlev = 2; e->nex = 2; e->ncl = 2; e->ndir = 2;
+        e->nlev = 2; e->nex = 2; e->ncl = 2;
         e->D = c->aspp_depth; e->Dp = pad64(e->D); e->LOW = c->low_dim; e->CATp = e->Dp + 64; e->C2 = c->c2_dim; e->h2 = c->c2_h; e->w2 = c->c2_w; e->R2 = e->B * e->h2 * e->w2;
+    }
+    if (e->bilstm) {
+        e->ndir = 2;
         const char* dn[2] = {"fw", "bw"};
         for (int d = 0; d < 2; ++d) {
             e->ldir[d].key = fmt("lstm_%s", dn[d]); e->ldir[d].pk = fmt("bidirectional_rnn/%s/lstm_cell/kernel", dn[d]); e->ldir[d].pb = fmt("bidirectional_rnn/%s/lstm_cell/bias", dn[d]);
@@ -2166,9 +2186,9 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
         if (e->dt == DT_F32) ECK(hipMemcpy(e->spatial, tmp, (size_t)reps * e->N * 64 * sizeof(float), hipMemcpyDeviceToDevice));
         else if (cmpc_cast(DT_F32, tmp, e->dt, e->spatial, (int64_t)reps * e->N * 64, nullptr) != CMPC_OK) { (void)hipFree(tmp); return fail(CMPC_EHIP); }
         ECK(hipDeviceSynchronize());
-        // the same grid with a constant 1 in channel 8: out += A^T D then carries sum_rows(D) in row 8 (the bias gradient of a convolution
-        // whose last input channels are the grid and whose bias follows its DW in the parameter layout)
-        for (size_t i = 0; i < (size_t)e->N; ++i) sp[i * 64 + 8] = 1.0f;
+        // the same grid with a constant 1 in channel sp (8; 11 behind the grid HSV): out += A^T D then carries sum_rows(D) in row sp (the bias
+        // gradient of a convolution whose last input channels are the grid and whose bias follows its DW in the parameter layout)
+        for (size_t i = 0; i < (size_t)e->N; ++i) sp[i * 64 + e->sp] = 1.0f;
         for (int b = 0; b < reps; ++b) ECK(hipMemcpy(tmp + (size_t)b * e->N * 64, sp.data(), sp.size() * sizeof(float), hipMemcpyHostToDevice));
         if (e->dt == DT_F32) ECK(hipMemcpy(e->spatial1, tmp, (size_t)reps * e->N * 64 * sizeof(float), hipMemcpyDeviceToDevice));
         else if (cmpc_cast(DT_F32, tmp, e->dt, e->spatial1, (int64_t)reps * e->N * 64, nullptr) != CMPC_OK) { (void)hipFree(tmp); return fail(CMPC_EHIP); }
@@ -2177,7 +2197,7 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
         e->mutan_bias_row = !getenv("CMPC_NO_BIAS_ROW");
         for (int i = 0; i < e->nlev && e->mutan_bias_row; ++i)
             for (int hd = 1; hd <= 5; ++hd)
-                if (poff(e, fmt("vis_trans_%s_head%d/biases", lvn(e, i), hd)) != poff(e, fmt("vis_trans_%s_head%d/DW", lvn(e, i), hd)) + (int64_t)(e->C + 8) * e->C) e->mutan_bias_row = false;
+                if (poff(e, fmt("vis_trans_%s_head%d/biases", lvn(e, i), hd)) != poff(e, fmt("vis_trans_%s_head%d/DW", lvn(e, i), hd)) + (int64_t)(e->C + e->sp) * e->C) e->mutan_bias_row = false;
     }
     if (e->vid) {
         std::vector<float> on(64, 1.0f);
@@ -2193,6 +2213,7 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
     for (auto& ev : e->evpool) { ev = nullptr; ECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); }
     ECK(hipEventCreateWithFlags(&e->ev_opt0, hipEventDisableTiming));
     ECK(hipEventCreateWithFlags(&e->ev_opt1, hipEventDisableTiming));
+    ECK(hipEventCreateWithFlags(&e->ev_grid_read, hipEventDisableTiming));
     for (auto& d : e->deferred) d.reserve(128);
     if (const char* v = getenv("CMPC_WGRAD_OVERLAP")) e->wgrad_overlap = atoi(v) != 0;       // read once, at create
     if (const char* v = getenv("CMPC_MUTAN_EPILOGUE")) e->mutan_epilogue = atoi(v) != 0;
@@ -2215,8 +2236,8 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
             e->bucket[3] = {{l3, ex0 - l3}, {lat0, par0 - lat0}};
             e->bucket[4] = {{0, lat0}, {par0, l5 - par0}};
         } else {
-            // CMPCv5_BiLSTM: 0 = exchange modules + ConvLSTM + ASPP + decoder, 1 = level c5, 2 = level c4 + score_c5 / score_c4 + laterals,
-            // 3 = (empty), 4 = text encoder (both LSTMs, words_feat) + parser
+            // v5 trunk: 0 = exchange modules + ConvLSTM + ASPP + decoder, 1 = level c5, 2 = level c4 + score_c5 / score_c4 + laterals,
+            // 3 = (empty), 4 = text encoder (CMPCv5_BiLSTM: both LSTMs, words_feat) + parser
             const int64_t lat0 = off("c5_lateral/DW"), par0 = off("words_parse_1/DW"), l5 = off("vis_trans_c5_head1/DW"), l4 = off("vis_trans_c4_head1/DW"),
                           ex0 = off("spa_graph_key_c4gv_f1/DW");
             e->bucket[0] = {{ex0, e->total - ex0}};
@@ -2470,7 +2491,7 @@ extern "C" int cmpc_launch_count(cmpc_handle e, int64_t* n) { if (!e || !n) retu
 extern "C" int cmpc_forward(cmpc_handle e, const cmpc_feeds* f, const cmpc_fetches* fetch, void* stream) {
     if (!e || !f || !f->words || !f->seq_len || !f->c4 || !f->c5) { cmpc_set_error("forward: null handle / feed"); return CMPC_EINVAL; }
     if (!e->v5 && !f->c3) { cmpc_set_error("forward: CMPC_model needs the c3 tap"); return CMPC_EINVAL; }
-    if (e->v5 && (!f->c2 || (e->cfg.hsv && !f->im))) { cmpc_set_error("forward: CMPCv5_BiLSTM needs the c2 tap (and the image feed for the HSV variant)"); return CMPC_EINVAL; }
+    if (e->v5 && (!f->c2 || (e->cfg.hsv && !f->im))) { cmpc_set_error("forward: the CMPCv5 models need the c2 tap (and the image feed for the HSV variants)"); return CMPC_EINVAL; }
     CK(set_device(e));
     hipStream_t main = (hipStream_t)stream;
     t_cur = e;
@@ -2496,10 +2517,11 @@ extern "C" int cmpc_forward(cmpc_handle e, const cmpc_feeds* f, const cmpc_fetch
     // the lanes, while the backbone (caller's side stream) is still running; each lane then waits for the visual features itself.
     hipStream_t st[3];
     CK(fork_lanes(e, main, st));
-    if (f->target_fine && e->cfg.n_lanes > 1) {
+    if (f->target_fine && e->cfg.n_lanes > 1 && !e->grads_pending) {
         // a training step: the backward pass's two clears (its accumulate-into region and the 304 MB gradient buffer, 40-60 us at the head of
         // cmpc_backward's serial chain) are issued here, on a lane, under the backbone -- nothing of the forward pass touches either, and the
-        // previous step's optimizer (the last reader of the gradients) is complete: params_ready(.., 1) above
+        // previous step's optimizer (the last reader of the gradients) is complete: params_ready(.., 1) above.  Not while the last backward's
+        // gradients are still unconsumed (a validation forward between cmpc_backward and the optimizer): cmpc_backward then clears them itself
         HCK(hipMemsetAsync(e->ws + e->zf_bytes, 0, e->zb_bytes, st[2]));
         HCK(hipMemsetAsync(e->grads, 0, (size_t)e->total * sizeof(float), st[2]));
         e->bwd_zeroed = true;
@@ -2512,10 +2534,15 @@ extern "C" int cmpc_forward(cmpc_handle e, const cmpc_feeds* f, const cmpc_fetch
     CK(mark(e, "fwd:feats_ready", st[0]));
     if (e->v5) {
         // hsv:120-126 (the image feed only) before the levels that read it; the decoder's low-level branch (backbone only) on the idle third lane
-        if (e->cfg.hsv) {
-            CK(cmpc_hsv_map(e->dt, f->im, e->hsv, 64, B, e->H, e->W, e->h, e->w, st[2]));
-            if (e->cfg.n_lanes > 1) { hipEvent_t ev = next_event(e); HCK(hipEventRecord(ev, st[2])); HCK(hipStreamWaitEvent(st[0], ev, 0)); HCK(hipStreamWaitEvent(st[1], ev, 0)); }
+        if (e->hsv_taps) CK(cmpc_hsv_map(e->dt, f->im, e->hsv, 64, B, e->H, e->W, e->h, e->w, st[2]));
+        if (e->hsv_grid) {
+            // CMPCv5_HSV_model.py:120-127,136-137: the HSV map becomes channels 8..10 of this step's grid (and of its bias-row copy).  The grid
+            // was last read by the previous cmpc_backward's weight-gradient products; ev_grid_read orders this write behind them even when the
+            // caller issues this forward on another stream than that backward (on the same stream the fork above already does)
+            HCK(hipStreamWaitEvent(st[2], e->ev_grid_read, 0));
+            CK(cmpc_hsv_grid(e->dt, f->im, e->spatial, e->mutan_bias_row ? e->spatial1 : nullptr, B, e->H, e->W, e->h, e->w, st[2]));
         }
+        if (e->cfg.hsv && e->cfg.n_lanes > 1) { hipEvent_t ev = next_event(e); HCK(hipEventRecord(ev, st[2])); HCK(hipStreamWaitEvent(st[0], ev, 0)); HCK(hipStreamWaitEvent(st[1], ev, 0)); }
         CK(decoder_low_fwd(e, st[2]));
     }
     const char* lvm[3] = {"fwd:level_c5_done", "fwd:level_c4_done", "fwd:level_c3_done"};
@@ -2596,7 +2623,7 @@ extern "C" int cmpc_backward(cmpc_handle e, void* stream) {
     static const bool hp = getenv("CMPC_HOST_PROFILE") != nullptr;
     double hp_t = host_now();
     if (!e->have_target || !e->seq_len_feed) { cmpc_set_error("backward: the last cmpc_forward had no target_fine"); return CMPC_EINVAL; }
-    if (e->v5 && !e->cfg.bn_train) { cmpc_set_error("backward: CMPCv5_BiLSTM trains with batch statistics (cfg.bn_train = 1, mode == 'train')"); return CMPC_EINVAL; }
+    if (e->v5 && !e->cfg.bn_train) { cmpc_set_error("backward: the CMPCv5 models train with batch statistics (cfg.bn_train = 1, mode == 'train')"); return CMPC_EINVAL; }
     CK(set_device(e));
     hipStream_t main = (hipStream_t)stream;
     t_cur = e;
@@ -2725,9 +2752,11 @@ extern "C" int cmpc_backward(cmpc_handle e, void* stream) {
     if (wg_done) HCK(hipStreamWaitEvent(main, wg_done, 0));
     CK(flush_bucket(e, main, E::NBK - 1));     // text encoder + parser
     CK(cmpc_fold_flush(&e->fold, main));       // (nothing is left; ends the collection)
+    HCK(hipEventRecord(e->ev_grid_read, main));     // every read of the grid (the levels' dW products, joined above) is behind this point
     CK(mark(e, "bwd:end", main));
     HOSTPROF("flush+fold");
     e->last_main = main;
+    e->grads_pending = true;
     e->launches_step = g_cmpc_launches - e->l0;
     return CMPC_OK;
 }
@@ -2757,6 +2786,7 @@ extern "C" int cmpc_optimizer_bucket(cmpc_handle e, int b, float gscale, void* s
         HCK(hipEventRecord(e->ev_opt1, st));
         CK(mark(e, "opt:end", st));
         e->opt_pending = true;
+        e->grads_pending = false;
     }
     if (lr_used) *lr_used = lr;
     e->launches_step = g_cmpc_launches - e->l0;

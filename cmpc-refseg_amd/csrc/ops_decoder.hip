@@ -327,6 +327,36 @@ __global__ __launch_bounds__(256) void hsv_map_kernel(const float* __restrict__ 
         for (int c0 = 8; c0 < ld; c0 += 8) st8<T>(out + p * ld + c0, z);
     }
 }
+// CMPCv5_HSV_model.py:120-127,136-137: the same HSV map as channels 8..10 of the spatial grid [B*h*w, 64] (spatial_hsv) and, with grid1, of the
+// grid's bias-row copy (constant 1 in channel 11).  Channels 8..15 of a row are one 8-wide store per grid: the position grid in 0..7 is never
+// touched, and nothing past channel 15 is written (the row is 64 wide)
+template <typename T>
+__global__ __launch_bounds__(256) void hsv_grid_kernel(const float* __restrict__ im, T* __restrict__ grid, T* __restrict__ grid1, int B, int H, int W,
+                                                      int h, int w, float mu_b, float mu_g, float mu_r) {
+    const long total = (long)B * h * w;
+    const float sy = (float)H / (float)h, sx = (float)W / (float)w;
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long)gridDim.x * 256) {
+        const int x = (int)(p % w), y = (int)((p / w) % h), b = (int)(p / ((long)w * h));
+        int y0, y1, x0, x1; float fy, fx;
+        interp_coef(y, sy, H, y0, y1, fy);
+        interp_coef(x, sx, W, x0, x1, fx);
+        float c[4][3];
+        const int ys[4] = {y0, y0, y1, y1}, xs[4] = {x0, x1, x0, x1};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float* px = im + (((long)b * H + ys[k]) * W + xs[k]) * 3;
+            rgb2hsv(px[2] + mu_r, px[1] + mu_g, px[0] + mu_b, c[k][0], c[k][1], c[k][2]);
+        }
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            const float top = c[0][e] + (c[1][e] - c[0][e]) * fx, bot = c[2][e] + (c[3][e] - c[2][e]) * fx;
+            v[e] = top + (bot - top) * fy;
+        }
+        st8<T>(grid + p * 64 + 8, v);
+        if (grid1) { v[3] = 1.0f; st8<T>(grid1 + p * 64 + 8, v); }
+    }
+}
 
 // array_ops.reverse_sequence on [B, T, ld] float rows: out[b, t] = in[b, t < len ? len - 1 - t : t]
 __global__ void reverse_sequence_kernel(const float* __restrict__ in, float* __restrict__ out, const int* __restrict__ seq_len, int T, int ld) {
@@ -486,6 +516,12 @@ extern "C" int cmpc_hsv_map(int dt, const float* im, void* out, int ld, int B, i
     CMPC_DISPATCH_DT(dt, hipLaunchKernelGGL((hsv_map_kernel<T>), dim3(grid_for((long)B * h * w)), dim3(256), 0, ST, im, (T*)out, ld, B, H, W, h, w,
                                              104.00698793f, 116.66876762f, 122.67891434f));
     return cmpc_check_launch("hsv_map");
+}
+extern "C" int cmpc_hsv_grid(int dt, const float* im, void* grid, void* grid1, int B, int H, int W, int h, int w, void* stream) {
+    if (!im || !grid || grid1 == grid || B < 1 || h < 1 || w < 1 || H < 1 || W < 1) { cmpc_set_error("hsv_grid: bad args"); return CMPC_EINVAL; }
+    CMPC_DISPATCH_DT(dt, hipLaunchKernelGGL((hsv_grid_kernel<T>), dim3(grid_for((long)B * h * w)), dim3(256), 0, ST, im, (T*)grid, (T*)grid1, B, H, W, h, w,
+                                             104.00698793f, 116.66876762f, 122.67891434f));
+    return cmpc_check_launch("hsv_grid");
 }
 extern "C" int cmpc_reverse_sequence(const float* in, float* out, const int* seq_len, int B, int T, int ld, void* stream) {
     if (!in || !out || !seq_len || in == out || B < 1 || T < 1) { cmpc_set_error("reverse_sequence: bad args (not in place)"); return CMPC_EINVAL; }

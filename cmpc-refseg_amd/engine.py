@@ -45,7 +45,7 @@ class Engine:
                   "mlp_dim", "rnn_size", "glove_dim", "parse_dim", "start_lr", "end_lr", "lr_power", "lr_decay_step", "weight_decay"):
             setattr(c, k, getattr(cfg, k))
         _lib.call("cmpc_default_cfg_model", C.byref(c), int(cfg.model), int(cfg.hsv))
-        if cfg.model == _lib.MODEL_V5_BILSTM:
+        if cfg.model in (_lib.MODEL_V5_BILSTM, _lib.MODEL_V5):
             for k in ("bn_train", "bn_decay", "c2_dim", "c2_h", "c2_w", "aspp_depth", "low_dim"):
                 setattr(c, k, getattr(cfg, k))
             for i, r in enumerate(cfg.aspp_rates):
@@ -80,7 +80,7 @@ class Engine:
         self.total = tot.value
         self.params, self.grads, self.m, self.v = (dev_tensor(x.value, (self.total,), 0, self.device) for x in (p, g, m, v))
         self._taps: Dict[str, torch.Tensor] = {}
-        # non-trainable variables (CMPCv5_BiLSTM: batch-norm moving statistics)
+        # non-trainable variables (the CMPCv5 models: batch-norm moving statistics)
         self.state_index: Dict[str, int] = {}
         cnt = C.c_int64()
         for i in range(lib.cmpc_state_count(h)):

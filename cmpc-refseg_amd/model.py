@@ -34,7 +34,8 @@ _EXG = ("c3", "c4", "c5", "c3_2", "c4_2", "c5_2")
 _LEVELS_V5 = ("c5", "c4")                              # CMPCv5_BiLSTM_model.py:134-137
 _EXG_V5 = ("c4", "c5", "c4_2", "c5_2")                 # :364-375
 MODELS = {"CMPC_model": (_lib.MODEL_CMPC, 0), "CMPCv5_BiLSTM_model": (_lib.MODEL_V5_BILSTM, 0), "CMPCv5_BiLSTM_HSV_model": (_lib.MODEL_V5_BILSTM, 1),
-          "CMPC_video_mm_tgraph_allvec": (_lib.MODEL_VIDEO, 0)}        # CMPC_video/CMPC_video_mm_tgraph_allvec.py (trainval_video.py:10,35)
+          "CMPC_video_mm_tgraph_allvec": (_lib.MODEL_VIDEO, 0),        # CMPC_video/CMPC_video_mm_tgraph_allvec.py (trainval_video.py:10,35)
+          "CMPCv5_model": (_lib.MODEL_V5, 0), "CMPCv5_HSV_model": (_lib.MODEL_V5, 1)}     # CMPCv5_model.py, CMPCv5_HSV_model.py (get_model.py:8,9)
 FRAME_IDX = (0, 4, 8, 12, 15)                          # CMPC_video_mm_tgraph_allvec.py:70
 
 
@@ -69,7 +70,10 @@ class LSTM_model(object):
             raise ValueError("model must be one of %s" % (sorted(MODELS),))
         self.model_name = model
         model_id, hsv = MODELS[model]
-        self.v5 = model_id == _lib.MODEL_V5_BILSTM
+        self.v5 = model_id in (_lib.MODEL_V5_BILSTM, _lib.MODEL_V5)      # the v5 trunk: levels c5 / c4, ASPP + decoder, slim batch-norm
+        self.bilstm = model_id == _lib.MODEL_V5_BILSTM
+        if model_id == _lib.MODEL_V5:
+            vf_h, vf_w = H // 8, W // 8               # CMPCv5_model.py:52-53: the keywords are accepted and ignored
         self.video = model_id == _lib.MODEL_VIDEO
         self.frames = frames
         if self.video and (batch_size != 1 or frames <= max(FRAME_IDX)):
@@ -322,8 +326,13 @@ class LSTM_model(object):
         for x in (_EXG_V5 if self.v5 else _EXG):
             out[f"exg_{x}"] = t(f"exg_{x}")
         if self.v5:
-            for k in ("bilstm_fw", "bilstm_bw", "aspp_branches", "aspp_image", "aspp", "dec_cat", "dec_net2") + (("hsv",) if self.cfg.hsv else ()):
+            for k in ("aspp_branches", "aspp_image", "aspp", "dec_cat", "dec_net2"):
                 out[k] = t(k)
+            if self.bilstm:
+                for k in ("bilstm_fw", "bilstm_bw") + (("hsv",) if self.cfg.hsv else ()):
+                    out[k] = t(k)
+            else:
+                out["spatial"] = t("spatial")       # CMPCv5_HSV_model: channels 8..10 hold this step's HSV map (spatial_hsv, :136-137)
         if self.video:
             out["ac_lang"] = t("ac_lang")
             for lv in _LEVELS:
@@ -337,7 +346,7 @@ class LSTM_model(object):
     def head(self, feats, words, seq_len, target=None, after=None, im=None, levels_done=None):
         """build_graph() on given backbone taps (CMPC_model.py:89-142): one cmpc_forward call.  Returns the fetch dict
         (views into the handle's workspace: valid until the next call).  `after`: event that marks `feats` complete.
-        feats = (c3, c4, c5), or (c2, c4, c5) for the CMPCv5_BiLSTM models, whose HSV variant also needs the image feed `im`."""
+        feats = (c3, c4, c5), or (c2, c4, c5) for the CMPCv5 models, whose HSV variants also need the image feed `im`."""
         with torch.cuda.device(self.device):
             f0, c4, c5 = [f.to(tdt(self.dt)).contiguous() for f in feats] if after is None else feats
             w = self._dev(words, torch.int32)
@@ -346,7 +355,7 @@ class LSTM_model(object):
             imd = None
             if self.v5 and self.cfg.hsv:
                 if im is None:
-                    raise ValueError("CMPCv5_BiLSTM_HSV_model needs the image feed (CMPCv5_BiLSTM_HSV_model.py:120-126)")
+                    raise ValueError("%s needs the image feed (CMPCv5_BiLSTM_HSV_model.py:120-126, CMPCv5_HSV_model.py:120-127)" % self.model_name)
                 imd = self._dev(im, torch.float32)
             if self.v5:
                 self.eng.forward(w, sl, None, c4, c5, tg, feats_ready=after, c2=f0, im=imd, levels_done=levels_done, feats_ready_lv=self._tap_events if after is not None else None)
@@ -602,7 +611,8 @@ class LSTM_model(object):
 
 def get_segmentation_model(name, **kwargs):
     """get_model.get_segmentation_model (get_model.py:15-17): name -> <module>.LSTM_model(**kwargs).  Built: CMPC_model,
-    CMPCv5_BiLSTM_model, CMPCv5_BiLSTM_HSV_model (get_model.py:1,10,11)."""
+    CMPCv5_model, CMPCv5_HSV_model, CMPCv5_BiLSTM_model, CMPCv5_BiLSTM_HSV_model (get_model.py:1,8-11) and CMPC_video_mm_tgraph_allvec.
+    CMPCv5_model / CMPCv5_HSV_model derive vf_h = H // 8, vf_w = W // 8 and ignore the keywords (CMPCv5_model.py:52-53)."""
     if name not in MODELS:
         raise ValueError("model %r is not built (have: %s)" % (name, ", ".join(sorted(MODELS))))
     return LSTM_model(model=name, **kwargs)

@@ -55,7 +55,7 @@ class HeadCfg:
     end_lr: float = 0.00001
     lr_power: float = 0.9
     weight_decay: float = 0.0005
-    # which graph (get_model.py:15-17): "CMPC_model" or "CMPCv5_BiLSTM_model" (+ hsv = CMPCv5_BiLSTM_HSV_model), and the latter's extra
+    # which graph (get_model.py:15-17): _lib.MODEL_* (+ hsv = the HSV variant of a CMPCv5 graph), and the CMPCv5 trunk's extra
     # constructor arguments / hard-coded sizes (CMPCv5_BiLSTM_model.py:42,88,153,196,208,225)
     model: int = 0
     hsv: int = 0

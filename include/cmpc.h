@@ -283,6 +283,10 @@ int cmpc_resize_bilinear_bwd(int dt, const void* dy, int lddy, void* dx, int ldd
 /* hsv:120-126: im f32 [B, H, W, 3] (BGR minus mean) -> + mean, reverse to RGB, tf.image.rgb_to_hsv, legacy bilinear to [h, w]: out [B*h*w, ld]
  * (3 channels, the rest of the row zero) */
 int cmpc_hsv_map(int dt, const float* im, void* out, int ld, int B, int H, int W, int h, int w, void* stream);
+/* CMPCv5_HSV_model.py:120-127,136-137: the same HSV map written into channels 8..10 of the spatial grid [B*h*w, 64] (spatial_hsv, 11 channels),
+ * and -- when grid1 != NULL -- of the grid's bias-row copy, which also gets its constant 1 in channel 11.  Each row's channels 8..15 are
+ * stored as one vector: channels 0..7 (the position grid) are left as they are, 12..15 are written as 0 */
+int cmpc_hsv_grid(int dt, const float* im, void* grid, void* grid1, int B, int H, int W, int h, int w, void* stream);
 /* array_ops.reverse_sequence of bidirectional_dynamic_rnn (v5:170-174) on [B, T, ld] float rows (not in place), and the time-major word ids of
  * the reversed sequences: out_tb[t * B + b] = words[b, t < len ? len - 1 - t : t] */
 int cmpc_reverse_sequence(const float* in, float* out, const int* seq_len, int B, int T, int ld, void* stream);
@@ -358,8 +362,10 @@ typedef struct {
                                            no GPU is touched; every compute entry point then returns CMPC_EINVAL) */
     /* which graph: get_model.get_segmentation_model(name) (get_model.py:15-17) */
     int model;                          /* CMPC_MODEL_CMPC (CMPC_model.py) or CMPC_MODEL_V5_BILSTM (CMPCv5_BiLSTM_model.py: BiLSTM encoder, levels c5 / c4,
-                                           one gated branch, 2-step ConvLSTM, ASPP + DeepLabv3+ decoder on res2b_relu with slim batch-norm) */
-    int hsv;                            /* model V5_BILSTM: CMPCv5_BiLSTM_HSV_model.py -- HSV of the image appended to the c5 / c4 taps (hsv:120-134) */
+                                           one gated branch, 2-step ConvLSTM, ASPP + DeepLabv3+ decoder on res2b_relu with slim batch-norm), CMPC_MODEL_VIDEO,
+                                           CMPC_MODEL_V5 (CMPCv5_model.py: the same trunk with CMPC_model's one-direction encoder, no tanh) */
+    int hsv;                            /* model V5_BILSTM: CMPCv5_BiLSTM_HSV_model.py -- HSV of the image appended to the c5 / c4 taps (hsv:120-134);
+                                           model V5: CMPCv5_HSV_model.py -- HSV of the image as channels 8..10 of the spatial grid (:136-144) */
     int bn_train;                       /* model V5_BILSTM: batch_norm(is_training = mode == 'train') (v5:153-154): 1 = batch statistics (+ moving-average
                                            updates in the train step), 0 = moving statistics */
     float bn_decay;                     /* batch_norm_decay (v5:42), 0.9997 */
@@ -379,9 +385,13 @@ typedef struct {
 #define CMPC_MODEL_VIDEO 2              /* CMPC_video/CMPC_video_mm_tgraph_allvec.py (BASELINE config 5): batch_size 1; feeds c3 / c4 / c5 are the taps of the
                                            sample_frames frames, [sample_frames, vf_h, vf_w, .]; words END-padded with seq_len = number of words (the host turns
                                            the reference's front padding + valid_idx around: the graph slices the pad steps away, vid:141-142) */
+#define CMPC_MODEL_V5 3                 /* CMPCv5_model.py / CMPCv5_HSV_model.py (hsv = 1): the V5_BILSTM trunk and decoder with lstm() of CMPC_model.py:144-164
+                                           (one direction, words_feat = l2-normalised outputs, seq_mask from all-zero rows; no words_feat conv), laterals and
+                                           gv_lang without tanh.  vf_h = H / 8, vf_w = W / 8 (CMPCv5_model.py:52-53; the caller derives them).  The HSV
+                                           variant needs cmpc_feeds.im and widens every vis_trans head and the fusion conv by the grid's 3 HSV rows */
 /* fills *cfg with the reference's defaults (CMPC_model.py:15-40), f16 storage (the 16-bit mode that meets the 1e-4 mean-IoU bar), 3 lanes, device 0 */
 int cmpc_default_cfg(cmpc_cfg* cfg);
-/* the same for a given model: CMPC_MODEL_V5_BILSTM sets loss_w = 0.8, 0.1, 0.1, 0 (v5:541-542), bn_train 1, bn_decay 0.9997, c2_dim 256, c2_h = H / 4,
+/* the same for a given model: CMPC_MODEL_V5_BILSTM and CMPC_MODEL_V5 set loss_w = 0.8, 0.1, 0.1, 0 (v5:541-542), bn_train 1, bn_decay 0.9997, c2_dim 256, c2_h = H / 4,
  * c2_w = W / 4, aspp_depth 256, low_dim 48, rates 6 / 12 / 18 -- vf_h, vf_w, H, W must be set by the caller BEFORE (v5:52-53 does not derive them) */
 int cmpc_default_cfg_model(cmpc_cfg* cfg, int model, int hsv);
 int cmpc_create(const cmpc_cfg* cfg, cmpc_handle* out);
@@ -421,8 +431,8 @@ typedef struct {
     const float* target_fine;   /* [B, H, W, 1] or NULL for inference (:69) */
     void* feats_ready;          /* optional hipEvent_t recorded (on any stream) once c3/c4/c5 are complete: the text encoder
                                    is enqueued first and only the pyramid levels wait for it; NULL = ordered on `stream` */
-    const void* c2;             /* model V5_BILSTM: res2b_relu [B, c2_h, c2_w, c2_dim] NHWC, cfg.dtype (v5:88); c3 is unused there (may be NULL) */
-    const float* im;            /* model V5_BILSTM with hsv: the image feed itself [B, H, W, 3] f32, BGR minus mean (v5:80; hsv:120-126) */
+    const void* c2;             /* models V5_BILSTM / V5: res2b_relu [B, c2_h, c2_w, c2_dim] NHWC, cfg.dtype (v5:88); c3 is unused there (may be NULL) */
+    const float* im;            /* models V5_BILSTM / V5 with hsv: the image feed itself [B, H, W, 3] f32, BGR minus mean (v5:80; hsv:120-126) */
     void* feats_ready_lv[3];    /* optional, per pyramid level (c5, c4, c3 -- for V5_BILSTM slot 2 is the res2b tap): hipEvent_t recorded once THAT tap is
                                    complete; a level's lane then waits for its own tap only (c3 leaves the backbone after res3, c4 after res4), NULL
                                    entries fall back to feats_ready */
@@ -439,7 +449,8 @@ typedef struct {                /* optional caller-owned device buffers the fetc
  * in-graph mIoU (:438-447,486-490).  Everything is enqueued on `stream` and the handle's lane streams (which fork
  * from and join into `stream`); nothing synchronises the host. */
 int cmpc_forward(cmpc_handle h, const cmpc_feeds* feeds, const cmpc_fetches* fetches, void* stream);
-/* tf.gradients(cost) of the last cmpc_forward (which must have had target_fine) into the flat gradient buffer:
+/* tf.gradients(cost) of the last cmpc_forward (which must have had target_fine) into the flat gradient buffer, which then holds them until the
+ * optimizer's last bucket has been enqueued: a cmpc_forward (with or without target_fine) issued in between leaves them intact.
  * d cls_loss_all / d theta; the L2 term (:433,446) and the x2 on biases (:462-475) are applied by the optimizer. */
 int cmpc_backward(cmpc_handle h, void* stream);
 /* event (hipEvent_t, caller-owned; NULL = none) that every later cmpc_backward records once the pyramid levels' backward is complete */
