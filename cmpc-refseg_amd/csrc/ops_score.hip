@@ -237,8 +237,10 @@ __global__ __launch_bounds__(256) void score_conv_bwd_w_kernel(const float* __re
 }
 
 // tf.image.resize_bilinear (align_corners=False, legacy): in = out_idx * (in_size / out_size) in
-// float32; lo = floor(in); hi = min(lo + 1, in_size - 1); lerp = in - lo.
+// float32; lo = floor(in); hi = min(lo + 1, in_size - 1); lerp = in - lo.  The product is rounded on its own (no contraction):
+// fused into fma(o, scale, -lo) the lerp came from the unrounded product, up to half an ulp of `in` off TF's at non-integer ratios.
 __device__ __forceinline__ void interp_coef(int o, float scale, int n_in, int& lo, int& hi, float& lerp) {
+#pragma clang fp contract(off)
     const float in = (float)o * scale;
     lo = (int)floorf(in);
     hi = min(lo + 1, n_in - 1);

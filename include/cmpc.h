@@ -145,10 +145,12 @@ int cmpc_mutan_bwd(int dt, void* Th, const float* g, const void* X1, const float
                    float* dg, int B, int N, int ld, int C, void* stream);
 
 /* ---- build_spa_graph softmaxes (CMPC_model.py:384-399): A0 [B,N,Tp] f32 = affinity/sqrt(C);
- *      gw_w = softmax_T(mask*pr*A0 + (1-mask)*FLT_MIN), gw_v = softmax_N(pr*A0)*mask.
+ *      gw_w = softmax_T(mask*pr*A0 + (1-mask)*float32.min), gw_v = softmax_N(pr*A0)*mask  (float32.min = -FLT_MAX: padded words leave the softmax).
  *      f32 copies are kept for backward, dt copies ([B,N,Tp], pad columns 0) feed the GEMMs -- */
 /*      scratch: B * ceil(N/64) * 128 floats (per-chunk column statistics) */
-/*      mask_after != 0: CMPCv5_BiLSTM_model.py:486-487 -- gw_w = mask * softmax_T(pr*A0): padded words stay in the softmax (their logit is 0) */
+/*      mask_after != 0: CMPCv5_BiLSTM_model.py:486-487 -- gw_w = mask * softmax_T(pr*A0): padded words stay in the softmax (their logit is 0).
+ *      pr is parse_R = parse * mask (0 for padded words); the backward forms dpr of valid words only and writes 0 for padded ones, whose
+ *      parse rows receive no gradient upstream (cmpc_parse_softmax_bwd masks them) */
 int cmpc_graph_softmax_fwd(int dt, int mask_after, const float* A0, const float* pr, const float* mask, float* gw_w, float* gw_v,
                            void* gw_w_t, void* gw_v_t, float* scratch, int B, int N, int T, int Tp, void* stream);
 int cmpc_graph_softmax_bwd(int dt, const float* dgw_w, const float* dgw_v, const float* gw_w, const float* gw_v,

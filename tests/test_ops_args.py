@@ -1,0 +1,109 @@
+"""CPU test: every documented limit of the op-level stage entry points (include/cmpc.h) returns CMPC_EINVAL (-1) with a message
+before anything is launched -- the library loads and these calls run without a GPU.  Only the checks an entry point makes before its
+first HIP call are listed here (read off each entry point: map_ok / ok / the explicit range checks sit at the top); the pointers are
+dummies that are never dereferenced."""
+import importlib
+
+import pytest
+
+L = importlib.import_module("cmpc-refseg_amd._lib")
+P = 1          # a non-NULL dummy device pointer: never read, the call returns first
+EINVAL = -1
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return L.load()
+
+
+def _rejects(lib, name, *args, msg=None):
+    rc = getattr(lib, name)(*args)
+    assert rc == EINVAL, f"{name}{args} returned {rc}"
+    err = lib.cmpc_last_error()
+    assert err, f"{name}: no message"
+    if msg is not None:
+        assert msg.encode() in err, (name, err)
+    return err
+
+
+# (C, ld, dt) rejected by map_ok (ops_norm.hip: ld <= 2048) / the 1024-column kernels (ops_fusion.hip, ops_convlstm.hip)
+def _bad_maps(max_ld):
+    return [(65, 64, 0), (24, 60, 1), (8, max_ld + 8, 2), (0, 64, 0), (24, 64, 3), (24, 64, -1)]
+
+
+def test_map_limits_ops_norm(lib):
+    for C, ld, dt in _bad_maps(2048):
+        _rejects(lib, "cmpc_act_bwd", dt, P, P, P, 0, 16, ld, ld, C, P, None, 0, 0, None)
+        _rejects(lib, "cmpc_wcolsum", dt, P, P, P, ld, 2, 8, ld, C, 1.0, None)
+        _rejects(lib, "cmpc_rowdot1", dt, P, P, ld, P, 2, 8, ld, C, 1.0, None)
+        _rejects(lib, "cmpc_rank1_update", dt, P, P, P, None, None, ld, 1.0, 1.0, 2, 8, ld, C, None)
+        _rejects(lib, "cmpc_l2norm_rows_fwd", dt, P, P, P, None, 16, ld, C, None)
+        _rejects(lib, "cmpc_l2norm_rows_bwd", dt, P, P, P, P, 16, ld, C, 0, None)
+        _rejects(lib, "cmpc_gconv_pre_fwd", dt, P, P, P, P, P, P, 2, 8, ld, C, None)
+        _rejects(lib, "cmpc_gconv_pre_bwd", dt, P, P, P, P, P, P, 0, P, P, P, P, 2, 8, ld, C, None)
+        _rejects(lib, "cmpc_gconv_post_fwd", dt, P, P, P, P, P, P, 2, 8, ld, C, None)
+        _rejects(lib, "cmpc_gconv_post_bwd", dt, P, P, P, P, P, P, P, P, P, P, 2, 8, ld, C, None)
+    assert b"C=65 ld=64" in _rejects(lib, "cmpc_l2norm_rows_fwd", 0, P, P, P, None, 16, 64, 65, None)
+    assert b"dtype" in _rejects(lib, "cmpc_l2norm_rows_fwd", 3, P, P, P, None, 16, 64, 24, None)
+    # ld itself is fine at the 2048 limit; 2056 is one column block too many
+    _rejects(lib, "cmpc_l2norm_rows_fwd", 0, P, P, P, None, 16, 2056, 2048, None, msg="2048")
+
+
+def test_act_bwd_stride_and_rows_per_sample(lib):
+    _rejects(lib, "cmpc_act_bwd", 0, P, P, P, 0, 16, 56, 64, 24, P, None, 0, 0, None, msg="stride")     # stride < ld
+    _rejects(lib, "cmpc_act_bwd", 1, P, P, P, 0, 16, 68, 64, 24, P, None, 0, 0, None, msg="stride")     # stride % 8
+    _rejects(lib, "cmpc_act_bwd", 2, P, P, P, 0, 16, 64, 64, 24, None, P, 64, 0, None, msg="rows_per_sample")
+    _rejects(lib, "cmpc_act_bwd", 0, P, P, P, 0, 16, 64, 64, 24, None, P, 64, 5, None, msg="rows_per_sample")   # 16 % 5
+    _rejects(lib, "cmpc_act_bwd", 0, P, P, P, 0, 16, 64, 64, 24, None, P, 64, -4, None, msg="rows_per_sample")
+
+
+def test_map_limits_ops_fusion_and_convlstm(lib):
+    ln = L.ConvLstmLn()
+    dln = L.ConvLstmDln()
+    for C, ld, dt in _bad_maps(1024):
+        _rejects(lib, "cmpc_mutan_fwd", dt, P, P, P, P, 2, 8, ld, C, 0, None)
+        _rejects(lib, "cmpc_mutan_bwd", dt, P, P, P, P, P, P, 2, 8, ld, C, None)
+        _rejects(lib, "cmpc_exchange_combine_fwd", dt, P, P, P, P, P, ld, P, P, 2, 8, ld, C, None)
+        _rejects(lib, "cmpc_exchange_combine_bwd", dt, P, P, P, P, P, P, P, ld, P, 0, P, P, P, P, None, None, 2, 8, ld, C, None)
+        _rejects(lib, "cmpc_convlstm_a", dt, P, None, P, P, P, 2, 8, ld, C, None)
+        _rejects(lib, "cmpc_convlstm_b", dt, P, None, P, ln, P, P, 2, 8, ld, C, None)
+        _rejects(lib, "cmpc_convlstm_c", dt, P, P, ln, P, P, P, 2, 8, ld, C, None)
+        _rejects(lib, "cmpc_convlstm_bwd", dt, P, P, P, None, P, P, P, P, ln, P, P, None, P, P, P, dln, P, P, 2, 8, ld, C, None)
+    _rejects(lib, "cmpc_mutan_fwd", 0, P, P, P, P, 2, 8, 1032, 1025, 0, None, msg="1024")
+    _rejects(lib, "cmpc_convlstm_a", 0, P, None, P, P, P, 2, 8, 1032, 1025, None, msg="1024")
+
+
+def test_graph_softmax_limits(lib):
+    for T, Tp in ((65, 65), (0, 8), (8, 4), (33, 72)):
+        _rejects(lib, "cmpc_graph_softmax_fwd", 0, 0, P, P, P, P, P, P, P, P, 2, 64, T, Tp, None, msg="Tp <= 64")
+        _rejects(lib, "cmpc_graph_softmax_bwd", 1, P, P, P, P, P, P, P, P, P, P, P, 2, 64, T, Tp, None, msg="Tp <= 64")
+    _rejects(lib, "cmpc_graph_softmax_fwd", 2, 1, P, P, P, P, P, P, P, None, 2, 64, 20, 24, None, msg="scratch")
+    _rejects(lib, "cmpc_graph_softmax_bwd", 2, P, P, P, P, P, P, P, P, P, P, None, 2, 64, 20, 24, None, msg="scratch")
+
+
+def test_lstm_limits(lib):
+    # lstm_seq: B <= 8, ld a multiple of 64 and <= 1024, R <= ld, every pointer given (the sync word above all)
+    for B, T, ld, R in ((9, 5, 64, 64), (0, 5, 64, 64), (1, 5, 1088, 1000), (1, 5, 72, 72), (1, 5, 32, 32), (1, 0, 64, 64), (1, 5, 64, 65)):
+        _rejects(lib, "cmpc_lstm_seq_fwd", P, P, 4 * ld, P, P, P, P, P, P, B, T, ld, R, None, msg="lstm_seq_fwd")
+        _rejects(lib, "cmpc_lstm_seq_bwd", P, 4 * ld, P, P, P, P, P, P, B, T, ld, R, None, msg="lstm_seq_bwd")
+    _rejects(lib, "cmpc_lstm_seq_fwd", P, P, 256, P, P, P, P, P, None, 2, 5, 64, 64, None)
+    _rejects(lib, "cmpc_lstm_seq_bwd", P, 256, P, P, P, P, P, None, 2, 5, 64, 64, None)
+    # lstm_bwd_step: B <= 8, 16-B aligned rows
+    for B, ld, ldw in ((9, 64, 256), (0, 64, 256), (2, 66, 264), (2, 64, 258)):
+        _rejects(lib, "cmpc_lstm_bwd_step", P, P, ldw, P, P, P, P, 0, P, ld, P, P, P, B, ld, ld, None, msg="lstm_bwd_step")
+
+
+def test_parse_and_pool_limits(lib):
+    for ncls, ld in ((1, 8), (9, 16), (5, 4)):
+        _rejects(lib, "cmpc_parse_softmax_fwd", P, ld, P, P, 10, ncls, None, msg="ncls")
+        _rejects(lib, "cmpc_parse_softmax_bwd", P, P, P, P, ld, 10, ncls, None, msg="ncls")
+    for ncls, lo, ps in ((0, 0, 4), (2, -1, 4), (3, 2, 4), (1, 5, 5), (2, 0, 9)):
+        _rejects(lib, "cmpc_lang_pool_fwd", P, P, P, P, 2, 20, 64, 64, ncls, lo, ps, None, msg="cls_lo")
+        _rejects(lib, "cmpc_lang_pool_bwd", P, P, P, P, P, P, P, 2, 20, 64, 64, ncls, lo, ps, None, msg="cls_lo")
+    _rejects(lib, "cmpc_lang_pool_fwd", P, P, P, P, 2, 65, 64, 64, 2, 0, 4, None, msg="T <= 64")
+    _rejects(lib, "cmpc_lang_pool_fwd", P, P, P, P, 2, 20, 2056, 2048, 2, 0, 4, None, msg="ld <= 2048")
+
+
+def test_upsample_target_needs_outputs(lib):
+    for loss, inter, uni in ((None, P, P), (P, None, P), (P, P, None)):
+        _rejects(lib, "cmpc_upsample_fwd", P, P, None, P, loss, inter, uni, 2, 40, 40, 320, 320, None, msg="required with target")
