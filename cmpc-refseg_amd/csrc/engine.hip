@@ -2071,7 +2071,10 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
     if (c->v_emb_dim < 8 || c->mlp_dim < 8 || c->glove_dim < 1 || c->parse_dim < 4 || c->vocab_size < 1) {
         cmpc_set_error("create: need v_emb_dim >= 8, mlp_dim >= 8, glove_dim >= 1, parse_dim >= 4, vocab_size >= 1"); return CMPC_EINVAL;
     }
-    if (pad64(c->v_emb_dim) > 2048 || pad64(c->mlp_dim) > 2048) { cmpc_set_error("create: v_emb_dim, mlp_dim <= 2048 (per-column registers of the map kernels)"); return CMPC_EINVAL; }
+    if (pad64(c->v_emb_dim) > 2048) { cmpc_set_error("create: v_emb_dim <= 2048 (per-column registers of the map kernels)"); return CMPC_EINVAL; }
+    // every model runs the ConvLSTM and the exchange modules on [*, pad64(mlp_dim)] maps: two column blocks of 512 at most, and peephole rows
+    // of mlp_dim floats read as float4
+    if (pad64(c->mlp_dim) > 1024 || c->mlp_dim % 4) { cmpc_set_error("create: mlp_dim a multiple of 4 with pad64(mlp_dim) <= 1024 (ConvLSTM, exchange modules)"); return CMPC_EINVAL; }
     if (c->n_lanes < 1 || c->n_lanes > 3) { cmpc_set_error("create: n_lanes must be 1, 2 or 3"); return CMPC_EINVAL; }
     if (c->model != CMPC_MODEL_CMPC && c->model != CMPC_MODEL_V5_BILSTM && c->model != CMPC_MODEL_VIDEO && c->model != CMPC_MODEL_V5) {
         cmpc_set_error("create: model must be CMPC_MODEL_CMPC (0), CMPC_MODEL_V5_BILSTM (1), CMPC_MODEL_VIDEO (2) or CMPC_MODEL_V5 (3)"); return CMPC_EINVAL;

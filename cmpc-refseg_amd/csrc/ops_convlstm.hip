@@ -12,6 +12,14 @@ __host__ inline int rows_grid(int N, int cap) { int g = (N + WPB - 1) / WPB; ret
 
 struct Sum2 { double a, b; };
 
+// 8 fp32 values of a row that holds M floats (a peephole row, a LayerNorm vector), from column c0 (< M).  M % 4 == 0: when the 8 columns
+// run past M (c0 = M - 4) only the first float4 is read and the rest is 0, so nothing past the row's end is touched
+__device__ __forceinline__ void ld8_row(const float* row, int c0, int M, float (&v)[8]) {
+    if (c0 + 8 <= M) { ld8<float>(row + c0, v); return; }
+    const float4 a = *reinterpret_cast<const float4*>(row + c0);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = v[5] = v[6] = v[7] = 0.f;
+}
+
 // this workgroup's pair of statistic `sidx` into the stat block (cmpc_common.h: the consumers add the pairs)
 __device__ __forceinline__ void flush_sums(double s1, double s2, double* stats, int sidx, double (*red)[WPB], int slot) {
     s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
@@ -61,7 +69,7 @@ __global__ __launch_bounds__(256) void clstm_a_kernel(T* __restrict__ Yg, const 
             if (c_prev) {
                 float c[8], wi[8], wf[8];
                 ld8<T>(c_prev + r * ld + c0, c);
-                if (c0 < M) { ld8<float>(W_ci + (long)n * M + c0, wi); ld8<float>(W_cf + (long)n * M + c0, wf); }   // M % 8 == 0 or tail masked below
+                if (c0 < M) { ld8_row(W_ci + (long)n * M, c0, M, wi); ld8_row(W_cf + (long)n * M, c0, M, wf); }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int m = c0 + e;
@@ -86,14 +94,14 @@ __global__ __launch_bounds__(256) void clstm_a_kernel(T* __restrict__ Yg, const 
 }
 
 
-// this lane's slice of a per-channel fp32 vector (LayerNorm gamma / beta): loaded once per wave
+// this lane's slice of a per-channel fp32 vector of M values (LayerNorm gamma / beta): loaded once per wave, 0 from column M on
 template <int NB>
-__device__ __forceinline__ void load_vec(const float* v, float (&out)[NB][8], int ld) {
+__device__ __forceinline__ void load_vec(const float* v, float (&out)[NB][8], int M) {
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
         const int c0 = k * 512 + lane * 8;
-        if (c0 < ld) ld8<float>(v + c0, out[k]);
+        if (c0 < M) ld8_row(v, c0, M, out[k]);
         else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) out[k][e] = 0.f;
@@ -116,8 +124,8 @@ __global__ __launch_bounds__(256) void clstm_b_kernel(T* __restrict__ Yg, const 
     ln_stats(sums, 1 * B + b, cnt, mi, ri);
     ln_stats(sums, 2 * B + b, cnt, mf, rf);
     float gj[NB][8], bj[NB][8], gi[NB][8], bi[NB][8], gf[NB][8], bf_[NB][8];
-    load_vec<NB>(ln.gamma[0], gj, ld); load_vec<NB>(ln.beta[0], bj, ld); load_vec<NB>(ln.gamma[1], gi, ld);
-    load_vec<NB>(ln.beta[1], bi, ld); load_vec<NB>(ln.gamma[2], gf, ld); load_vec<NB>(ln.beta[2], bf_, ld);
+    load_vec<NB>(ln.gamma[0], gj, M); load_vec<NB>(ln.beta[0], bj, M); load_vec<NB>(ln.gamma[1], gi, M);
+    load_vec<NB>(ln.beta[1], bi, M); load_vec<NB>(ln.gamma[2], gf, M); load_vec<NB>(ln.beta[2], bf_, M);
     double so1 = 0, so2 = 0, sc1 = 0, sc2 = 0;
     for (int n = blockIdx.x * WPB + w; n < N; n += gridDim.x * WPB) {
         const long r = (long)b * N + n;
@@ -131,7 +139,7 @@ __global__ __launch_bounds__(256) void clstm_b_kernel(T* __restrict__ Yg, const 
             ld8<T>(y + c0, j); ld8<T>(y + ld + c0, i); ld8<T>(y + 2 * ld + c0, f); ld8<T>(y + 3 * ld + c0, o);
             if (c_prev) ld8<T>(c_prev + r * ld + c0, c);
             float wo[8];
-            if (c0 < M) ld8<float>(W_co + (long)n * M + c0, wo);
+            if (c0 < M) ld8_row(W_co + (long)n * M, c0, M, wo);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int m = c0 + e;
@@ -170,7 +178,7 @@ __global__ __launch_bounds__(256) void clstm_c_kernel(const T* __restrict__ Yg, 
     ln_stats(sums, 3 * B + b, cnt, mo, ro);
     ln_stats(sums, 4 * B + b, cnt, mc, rc);
     float go[NB][8], bo[NB][8], gc[NB][8], bc[NB][8];
-    load_vec<NB>(ln.gamma[3], go, ld); load_vec<NB>(ln.beta[3], bo, ld); load_vec<NB>(ln.gamma[4], gc, ld); load_vec<NB>(ln.beta[4], bc, ld);
+    load_vec<NB>(ln.gamma[3], go, M); load_vec<NB>(ln.beta[3], bo, M); load_vec<NB>(ln.gamma[4], gc, M); load_vec<NB>(ln.beta[4], bc, M);
     for (int n = blockIdx.x * WPB + w; n < N; n += gridDim.x * WPB) {
         const long r = (long)b * N + n;
 #pragma unroll
@@ -206,7 +214,7 @@ __global__ __launch_bounds__(256) void clstm_bwd1_kernel(const T* __restrict__ d
     ln_stats(sums, 3 * B + b, cnt, mo, ro);
     ln_stats(sums, 4 * B + b, cnt, mc, rc);
     float go[NB][8], bo[NB][8], gc[NB][8], bc[NB][8];
-    load_vec<NB>(ln.gamma[3], go, ld); load_vec<NB>(ln.beta[3], bo, ld); load_vec<NB>(ln.gamma[4], gc, ld); load_vec<NB>(ln.beta[4], bc, ld);
+    load_vec<NB>(ln.gamma[3], go, M); load_vec<NB>(ln.beta[3], bo, M); load_vec<NB>(ln.gamma[4], gc, M); load_vec<NB>(ln.beta[4], bc, M);
     float ago[NB][8], abo[NB][8], agc[NB][8], abc[NB][8];
 #pragma unroll
     for (int k = 0; k < NB; ++k)
@@ -272,7 +280,7 @@ __global__ __launch_bounds__(256) void clstm_bwd2_kernel(const T* __restrict__ Y
     stat_means(bsums_in, 4 * B + b, cnt, c_m1, c_m2);
     float gq[3][NB][8], bq[3][NB][8];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) { load_vec<NB>(ln.gamma[q], gq[q], ld); load_vec<NB>(ln.beta[q], bq[q], ld); }
+    for (int q = 0; q < 3; ++q) { load_vec<NB>(ln.gamma[q], gq[q], M); load_vec<NB>(ln.beta[q], bq[q], M); }
     float ag[3][NB][8], ab[3][NB][8];
 #pragma unroll
     for (int q = 0; q < 3; ++q)
@@ -295,7 +303,7 @@ __global__ __launch_bounds__(256) void clstm_bwd2_kernel(const T* __restrict__ Y
                 if (c_prev) ld8<T>(c_prev + r * ld + c0, c);
                 ld8<T>(dYg + r * 4 * ld + 3 * ld + c0, dxo); ld8<T>(scr + r * ld + c0, dxc);
                 float wo[8];
-                if (c0 < M) ld8<float>(W_co + (long)n * M + c0, wo);
+                if (c0 < M) ld8_row(W_co + (long)n * M, c0, M, wo);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int m = c0 + e;
@@ -364,7 +372,7 @@ __global__ __launch_bounds__(256) void clstm_bwd3_kernel(const T* __restrict__ Y
 #pragma unroll
             for (int q = 0; q < 3; ++q) { ld8<T>(Yg + r * 4 * ld + q * ld + c0, x[q]); ld8<T>(dYg + r * 4 * ld + q * ld + c0, d[q]); }
             float wi[8], wf[8];
-            if (c_prev) { ld8<T>(c_prev + r * ld + c0, c); ld8<T>(dc_prev + r * ld + c0, dcp); if (c0 < M) { ld8<float>(W_ci + (long)n * M + c0, wi); ld8<float>(W_cf + (long)n * M + c0, wf); } }
+            if (c_prev) { ld8<T>(c_prev + r * ld + c0, c); ld8<T>(dc_prev + r * ld + c0, dcp); if (c0 < M) { ld8_row(W_ci + (long)n * M, c0, M, wi); ld8_row(W_cf + (long)n * M, c0, M, wf); } }
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int m = c0 + e;
@@ -423,7 +431,9 @@ __global__ __launch_bounds__(256) void clstm_peephole_grad_kernel(const T* __res
 }
 
 bool ok(const char* what, int dt, int ld, int M) {
-    if (ld <= 0 || M <= 0 || M > ld || ld % 8 || ld > MB * 512) { cmpc_set_error("%s: need 0 < M <= ld <= %d, ld %% 8 == 0", what, MB * 512); return false; }
+    if (ld <= 0 || M <= 0 || M > ld || ld % 8 || ld > MB * 512 || M % 4) {     // M % 4: the peephole rows are read as float4
+        cmpc_set_error("%s: need 0 < M <= ld <= %d, ld %% 8 == 0, M %% 4 == 0", what, MB * 512); return false;
+    }
     if (dt != DT_F32 && dt != DT_BF16 && dt != DT_F16) { cmpc_set_error("%s: bad dtype", what); return false; }
     return true;
 }

@@ -19,8 +19,9 @@ __host__ __device__ inline int lanes_per_row(int ld) {
 constexpr int BN_ROWS = 128;      // rows per workgroup of the statistics kernels (4 waves x 32)
 constexpr int BN_MB = 4;          // column blocks of 512 per lane: ld <= 2048
 
-// sums over the rows of s0 = f(x) and s1 = g(x) per channel; MODE 0: (x, x^2) for the forward statistics;
-// MODE 1: (dy*[y>0], dy*[y>0]*xhat) for the backward pass (relu gate through the OUTPUT y)
+// sums over the rows of s0 = f(x) and s1 = g(x) per channel; MODE 0: (x - x0, (x - x0)^2) for the forward statistics, shifted by the
+// channel's value in row 0 (x0, which workgroup 0 also stores after the partial rows) so that the float32 sums of squares do not cancel
+// when |mean| >> std; MODE 1: (dy*[y>0], dy*[y>0]*xhat) for the backward pass (relu gate through the OUTPUT y)
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ x, int ldx, const T* __restrict__ dy, int lddy, const T* __restrict__ y, int ldy,
                                                         const float* __restrict__ mean_rstd, int Cpad, int relu, double* __restrict__ part, int R, int C) {
@@ -32,11 +33,21 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ x
     for (int k = 0; k < BN_MB; ++k)
 #pragma unroll
         for (int e = 0; e < 8; ++e) { a0[k][e] = 0.f; a1[k][e] = 0.f; mu[k][e] = 0.f; rsd[k][e] = 0.f; }
-    if (MODE == 1) {
+#pragma unroll
+    for (int k = 0; k < BN_MB; ++k) {
+        const int c0 = k * 512 + cgp * 8;
+        if (c0 < ldw) {
+            if (MODE == 1) { ld8<float>(mean_rstd + c0, mu[k]); ld8<float>(mean_rstd + Cpad + c0, rsd[k]); }
+            else ld8<T>(x + c0, mu[k]);                                 // the shift x0 (row 0)
+        }
+    }
+    if (MODE == 0 && blockIdx.x == 0 && w == 0 && rs == 0) {
 #pragma unroll
         for (int k = 0; k < BN_MB; ++k) {
             const int c0 = k * 512 + cgp * 8;
-            if (c0 < ldw) { ld8<float>(mean_rstd + c0, mu[k]); ld8<float>(mean_rstd + Cpad + c0, rsd[k]); }
+            if (c0 < ldw)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) part[(long)gridDim.x * 2 * Cpad + c0 + e] = (double)mu[k][e];
         }
     }
     const int r_begin = blockIdx.x * BN_ROWS + w * (BN_ROWS / 4), r_end = min(R, r_begin + BN_ROWS / 4);
@@ -49,7 +60,7 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ x
                 ld8<T>(x + (long)r * ldx + c0, xv);
                 if (MODE == 0) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { a0[k][e] += xv[e]; a1[k][e] += xv[e] * xv[e]; }
+                    for (int e = 0; e < 8; ++e) { const float d = xv[e] - mu[k][e]; a0[k][e] += d; a1[k][e] += d * d; }
                 } else {
                     float dv[8], yv[8];
                     ld8<T>(dy + (long)r * lddy + c0, dv);
@@ -107,16 +118,18 @@ __device__ __forceinline__ bool fold_parts(const double* __restrict__ part, int 
     for (int k = 0; k < FOLD_S; ++k) { s0 += red[0][k][cl]; s1 += red[1][k][cl]; }
     return true;
 }
-// fold of the forward partials: sums[2][Cpad] (float64: kept for the moving-statistics update) and mean_rstd[2][Cpad]
+// fold of the forward partials: sums[2][Cpad] = {sum x, sum x^2} (float64, rebuilt from the shifted sums: kept for the moving-statistics
+// update) and mean_rstd[2][Cpad]
 __global__ __launch_bounds__(FOLD_C * FOLD_S) void bn_stats_finish_kernel(const double* __restrict__ part, int nparts, double* __restrict__ sums, float* __restrict__ mean_rstd,
                                                                         int R, int C, int Cpad, float eps) {
     int c; double s0, s1;
     if (!fold_parts(part, nparts, C, Cpad, c, s0, s1)) return;
-    sums[c] = s0; sums[Cpad + c] = s1;
-    const double m = s0 / R;
-    double var = s1 / R - m * m;
+    const double x0 = c < C ? part[(long)nparts * 2 * Cpad + c] : 0.0;
+    sums[c] = s0 + R * x0; sums[Cpad + c] = s1 + x0 * (2.0 * s0 + R * x0);
+    const double d = s0 / R;
+    double var = s1 / R - d * d;
     if (var < 0.0) var = 0.0;
-    mean_rstd[c] = c < C ? (float)m : 0.f;
+    mean_rstd[c] = c < C ? (float)(x0 + d) : 0.f;
     mean_rstd[Cpad + c] = c < C ? (float)(1.0 / sqrt(var + (double)eps)) : 0.f;
 }
 // inference mode: mean / rstd from the moving statistics
@@ -225,7 +238,10 @@ __global__ __launch_bounds__(256) void bn_apply_bwd_kernel(const T* __restrict__
 
 // tf.image.resize_bilinear (align_corners=False, legacy): in = out_idx * (in_size / out_size) in float32; lo = floor(in);
 // hi = min(lo + 1, in_size - 1); lerp = in - lo; value = top + (bot - top) * ly with top = tl + (tr - tl) * lx
+// The product o * scale is rounded to float before lerp = in - lo: with contraction the compiler fuses the two into one FMA and the
+// weight comes from the unrounded product (off by up to half an ulp of `in` at non-integer ratios)
 __device__ __forceinline__ void interp_coef(int o, float scale, int n_in, int& lo, int& hi, float& lerp) {
+#pragma clang fp contract(off)
     const float in = (float)o * scale;
     lo = (int)floorf(in);
     hi = min(lo + 1, n_in - 1);
@@ -456,7 +472,7 @@ bool bn_ok(const char* what, int ld, int C, int Cpad) {
 extern "C" int cmpc_bn_stats(int dt, const void* x, int ldx, int R, int C, int Cpad, float eps, double* sums, float* mean_rstd, void* stream) {
     if (!x || !sums || !mean_rstd || R < 1 || !bn_ok("bn_stats", ldx, C, Cpad)) { if (R < 1 || !x || !sums || !mean_rstd) cmpc_set_error("bn_stats: bad args"); return CMPC_EINVAL; }
     const int nparts = (R + BN_ROWS - 1) / BN_ROWS;
-    double* part = (double*)cmpc_ws((size_t)nparts * 2 * Cpad * sizeof(double), ST);
+    double* part = (double*)cmpc_ws((size_t)(nparts * 2 + 1) * Cpad * sizeof(double), ST);       // + the shift row
     if (!part) return CMPC_EHIP;
     CMPC_DISPATCH_DT(dt, hipLaunchKernelGGL((bn_partial_kernel<T, 0>), dim3(nparts), dim3(256), 8 * Cpad * sizeof(double), ST, (const T*)x, ldx, (const T*)nullptr, 0,
                                              (const T*)nullptr, 0, (const float*)nullptr, Cpad, 0, part, R, C));

@@ -193,7 +193,8 @@ int cmpc_exchange_combine_bwd(int dt, const void* dout, const void* out, const f
  *      in the order j,i,f,o,c; sums / bsums are stat blocks of 5*B statistics, [j,i,f,o,c][B] -- */
 typedef struct { const float* beta[5]; const float* gamma[5]; } cmpc_convlstm_ln;
 typedef struct { float* dbeta[5]; float* dgamma[5]; } cmpc_convlstm_dln;
-/* A: i += W_ci*c_prev, f += W_cf*c_prev (skipped when c_prev NULL); sums[j,i,f] <- stats */
+/* every entry point: 0 < M <= ld <= 1024, ld % 8 == 0, M % 4 == 0 (the peephole rows and LayerNorm vectors hold M floats, read as float4)
+ * A: i += W_ci*c_prev, f += W_cf*c_prev (skipped when c_prev NULL); sums[j,i,f] <- stats */
 int cmpc_convlstm_a(int dt, void* Yg, const void* c_prev, const float* W_ci, const float* W_cf, double* sums,
                     int B, int N, int ld, int M, void* stream);
 /* B: c_pre = c_prev*sig(LN f + 1) + sig(LN i)*tanh(LN j); o_pre = o + W_co*c_pre (in place);
@@ -290,10 +291,11 @@ int cmpc_hsv_map(int dt, const float* im, void* out, int ld, int B, int H, int W
  * stored as one vector: channels 0..7 (the position grid) are left as they are, 12..15 are written as 0 */
 int cmpc_hsv_grid(int dt, const float* im, void* grid, void* grid1, int B, int H, int W, int h, int w, void* stream);
 /* array_ops.reverse_sequence of bidirectional_dynamic_rnn (v5:170-174) on [B, T, ld] float rows (not in place), and the time-major word ids of
- * the reversed sequences: out_tb[t * B + b] = words[b, t < len ? len - 1 - t : t] */
+ * the reversed sequences: out_tb[t * B + b] = words[b, t < len ? len - 1 - t : t].  len = seq_len[b] clamped to [0, T]: a negative length
+ * copies the row unchanged, one above T reverses all T steps */
 int cmpc_reverse_sequence(const float* in, float* out, const int* seq_len, int B, int T, int ld, void* stream);
 int cmpc_reverse_words_tb(const int* words, const int* seq_len, int* out_tb, int B, int T, void* stream);
-/* seq_mask of v5:181: mask[r] = (sum_c |a[r, c]| + |b[r, c]|) != 0 */
+/* seq_mask of v5:181: mask[r] = (sum_c |a[r, c]| + |b[r, c]|) != 0 over c < C (NaN and inf count as non-zero; columns C..ld are not read) */
 int cmpc_rows_nonzero2(const float* a, const float* b, float* mask, int rows, int ld, int C, void* stream);
 /* the decoder's last 1x1 convolution to ONE channel (v5:205): out[r] = x[r, :C] . w + bias[0]; backward: dx[r, :] = d[r] * w, dw += sum_r d[r] x[r, :],
  * dbias += sum_r d[r] */

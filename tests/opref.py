@@ -148,6 +148,14 @@ def run_twice(fn):
     return a
 
 
+def bilinear_axis(n_in, n_out):
+    """legacy resize_bilinear coefficients as the TF kernel computes them (interp_coef of ops_score.hip / ops_decoder.hip): in = out_idx *
+    (in / out) in float32, lo = floor(in), hi = min(lo + 1, in - 1), lerp = in - lo (float32, returned as float64)"""
+    src = torch.arange(n_out, dtype=torch.float32) * torch.tensor(n_in / n_out, dtype=torch.float32)
+    lo = torch.floor(src)
+    return lo.long(), torch.clamp(lo.long() + 1, max=n_in - 1), (src - lo).double()
+
+
 # ----------------------------------------------------------------------------------------------------------------------------
 # shapes
 # ----------------------------------------------------------------------------------------------------------------------------

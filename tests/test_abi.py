@@ -184,3 +184,24 @@ def test_engine_rejects_bad_configs(pkg):
         setattr(c, field, old)
     assert lib.cmpc_create(None, ctypes.byref(h)) == -1
     assert lib.cmpc_tap(None, b"up", None, None, None, None) == -1
+
+
+def test_engine_mlp_dim_limits(pkg):
+    """Every model runs the ConvLSTM and the exchange modules on [*, pad64(mlp_dim)] maps: mlp_dim must be a multiple of 4 (the peephole rows
+    are read as float4) with pad64(mlp_dim) <= 1024 (two column blocks), checked by planning-only handles"""
+    lib = pkg._lib.load()
+    for model, hsv in ((0, 0), (1, 1), (2, 0), (3, 1)):
+        c = pkg._lib.EngineCfg()
+        assert lib.cmpc_default_cfg(ctypes.byref(c)) == 0 and lib.cmpc_default_cfg_model(ctypes.byref(c), model, hsv) == 0
+        c.device = -1
+        if model == 2:
+            c.batch_size = 1                        # the video graph is batch 1
+        h = ctypes.c_void_p()
+        for bad in (37, 1100, 1026, 502):
+            c.mlp_dim = bad
+            assert lib.cmpc_create(ctypes.byref(c), ctypes.byref(h)) == -1, (model, bad)
+            assert b"mlp_dim" in lib.cmpc_last_error(), (model, bad)
+        for good in (1024, 500, 8):
+            c.mlp_dim = good
+            assert lib.cmpc_create(ctypes.byref(c), ctypes.byref(h)) == 0, (model, good, lib.cmpc_last_error())
+            assert lib.cmpc_destroy(h) == 0

@@ -87,19 +87,11 @@ UP_SHAPES = [(2, 40, 40, 320, 320), (1, 7, 7, 50, 50), (3, 40, 40, 321, 321), (2
              (1, 13, 17, 104, 136), (8, 5, 5, 5, 5)]
 
 
-def _axis(n_in, n_out):
-    """legacy resize_bilinear coefficients as the TF kernel computes them (ops_score.hip interp_coef): in = out_idx * (in / out) in
-    float32, lo = floor(in), hi = min(lo + 1, in - 1), lerp = in - lo (float32)"""
-    src = torch.arange(n_out, dtype=torch.float32) * torch.tensor(n_in / n_out, dtype=torch.float32)
-    lo = torch.floor(src)
-    return lo.long(), torch.clamp(lo.long() + 1, max=n_in - 1), (src - lo).double()
-
-
 def _up_ref(score, H, W):
     """O.resize_bilinear's lerp order, in float64 on the float32 coefficients (O.resize_bilinear takes float64 lerps for float64 input)"""
     B, h, w = score.shape
-    ylo, yhi, yl = _axis(h, H)
-    xlo, xhi, xl = _axis(w, W)
+    ylo, yhi, yl = R.bilinear_axis(h, H)
+    xlo, xhi, xl = R.bilinear_axis(w, W)
     top, bot = score[:, ylo], score[:, yhi]
     t = top[:, :, xlo] + (top[:, :, xhi] - top[:, :, xlo]) * xl
     b = bot[:, :, xlo] + (bot[:, :, xhi] - bot[:, :, xlo]) * xl

@@ -107,3 +107,48 @@ def test_parse_and_pool_limits(lib):
 def test_upsample_target_needs_outputs(lib):
     for loss, inter, uni in ((None, P, P), (P, None, P), (P, P, None)):
         _rejects(lib, "cmpc_upsample_fwd", P, P, None, P, loss, inter, uni, 2, 40, 40, 320, 320, None, msg="required with target")
+
+
+def test_convlstm_needs_m_multiple_of_4(lib):
+    # the peephole rows (W_c* [N, M]) are read as float4: M % 4 == 0 (M = 500, the product's, passes the check)
+    ln, dln = L.ConvLstmLn(), L.ConvLstmDln()
+    for M in (37, 22, 510):
+        _rejects(lib, "cmpc_convlstm_a", 0, P, None, P, P, P, 2, 8, 512, M, None, msg="M % 4")
+        _rejects(lib, "cmpc_convlstm_b", 1, P, None, P, ln, P, P, 2, 8, 512, M, None, msg="M % 4")
+        _rejects(lib, "cmpc_convlstm_c", 2, P, P, ln, P, P, P, 2, 8, 512, M, None, msg="M % 4")
+        _rejects(lib, "cmpc_convlstm_bwd", 0, P, P, P, None, P, P, P, P, ln, P, P, None, P, P, P, dln, P, P, 2, 8, 512, M, None, msg="M % 4")
+
+
+def test_decoder_limits(lib):
+    # batch norm: 1 <= C <= Cpad <= 2048, Cpad % 8 == 0, the x row stride a multiple of 8 and >= roundup(C, 8), R >= 1
+    for C, Cpad, ld, R in ((0, 8, 8, 4), (9, 8, 16, 4), (8, 12, 8, 4), (2049, 2056, 2056, 4), (8, 8, 12, 4), (9, 16, 8, 4), (8, 8, 8, 0)):
+        _rejects(lib, "cmpc_bn_stats", 0, P, ld, R, C, Cpad, 1e-5, P, P, None)
+        _rejects(lib, "cmpc_bn_apply_fwd", 1, P, ld, P, Cpad, P, P, P, 16, 16, R, C, 1, None)
+        _rejects(lib, "cmpc_bn_bwd", 2, P, 16, P, 16, P, ld, P, Cpad, P, P, 16, P, P, P, R, C, 1, None, msg="bn_bwd")
+    _rejects(lib, "cmpc_bn_stats", 0, P, 64, 10, 24, 2056, 1e-5, P, P, None, msg="2048")
+    # bn_apply_fwd: Cy % 8 == 0, Cy >= C, Cy <= 2048, ldy % 8 == 0
+    for Cy, ldy in ((20, 24), (16, 24), (24, 28), (2056, 2056)):
+        _rejects(lib, "cmpc_bn_apply_fwd", 0, P, 24, P, 24, P, P, P, ldy, Cy, 10, 20 if Cy != 16 else 24, 0, None)
+    # bn_bwd: relu needs y; 16-B aligned row strides
+    _rejects(lib, "cmpc_bn_bwd", 0, P, 24, None, 24, P, 24, P, 24, P, P, 24, P, P, P, 10, 20, 1, None, msg="bn_bwd")
+    _rejects(lib, "cmpc_bn_bwd", 0, P, 20, None, 24, P, 24, P, 24, P, P, 24, P, P, P, 10, 20, 0, None, msg="bn_bwd")
+    _rejects(lib, "cmpc_bn_bwd", 0, P, 24, None, 24, P, 24, P, 24, P, P, 28, P, P, P, 10, 20, 0, None, msg="bn_bwd")
+    _rejects(lib, "cmpc_bn_from_moving", P, P, 10, 8, 1e-5, P, None, msg="bn_from_moving")
+    _rejects(lib, "cmpc_bn_update_moving", P, 0, 0.9, P, P, 8, 8, None, msg="bn_update_moving")
+    _rejects(lib, "cmpc_bn_update_moving", P, 4, 0.9, P, P, 10, 8, None, msg="bn_update_moving")
+    # resize: C % 8 == 0 and >= 8, 16-B rows, sizes >= 1
+    for C, ldx, ldy, h in ((12, 16, 16, 4), (0, 16, 16, 4), (16, 20, 16, 4), (16, 16, 20, 4), (16, 16, 16, 0)):
+        _rejects(lib, "cmpc_resize_bilinear_fwd", 0, P, ldx, P, ldy, 2, h, 4, 8, 8, C, None, msg="resize_bilinear_fwd")
+        _rejects(lib, "cmpc_resize_bilinear_bwd", 1, P, ldy, P, ldx, 2, h, 4, 8, 8, C, None, msg="resize_bilinear_bwd")
+    # hsv: ld % 8 == 0 and >= 8; grid1 != grid
+    for ld in (4, 12):
+        _rejects(lib, "cmpc_hsv_map", 0, P, P, ld, 1, 8, 8, 4, 4, None, msg="hsv_map")
+    _rejects(lib, "cmpc_hsv_grid", 0, P, P, P, 1, 8, 8, 4, 4, None, msg="hsv_grid")
+    # reverse_sequence: not in place, T >= 1
+    _rejects(lib, "cmpc_reverse_sequence", P, P, P, 2, 5, 16, None, msg="not in place")
+    _rejects(lib, "cmpc_reverse_sequence", P, 2, P, 2, 0, 16, None, msg="reverse_sequence")
+    # conv_to1: ld % 8 == 0, C <= ld, R >= 1; the backward's column registers end at 2048
+    for R, C, ld in ((10, 8, 12), (10, 24, 16), (0, 8, 8)):
+        _rejects(lib, "cmpc_conv_to1_fwd", 0, P, ld, P, P, P, R, C, None, msg="conv_to1_fwd")
+        _rejects(lib, "cmpc_conv_to1_bwd", 0, P, P, ld, P, P, P, P, R, C, None, msg="conv_to1_bwd")
+    _rejects(lib, "cmpc_conv_to1_bwd", 1, P, P, 2056, P, P, P, P, 10, 2050, None, msg="conv_to1_bwd")
