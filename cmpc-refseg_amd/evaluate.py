@@ -8,6 +8,12 @@ Every sample keeps its ORIGINAL size (build_batches.py:63-66 resizes only the tr
 
     ev = Evaluator(model); ev.add(ids, seq_len, image, gt_mask) ...; ev.result()
 
+The video model (CMPC_video_mm_tgraph_allvec, batch 1) on an A2D split (CMPC_video/trainval_video.py:136-291) goes through VideoEvaluator:
+one clip per forward pass, the 5 sampled frames (plus the key image for DenseCRF) resized by one cmpc_eval_prep launch, the forward pass on
+that device feed (LSTM_model.forward_video_frames), I / U by cmpc_eval_mask_iu at the mask's size, precision at the driver's ten thresholds:
+
+    ev = VideoEvaluator(model); ev.add(text_batch, im_batch, frames, mask_batch) ...; ev.result()
+
 Host work per batch is packing uint8 bytes and descriptors into a pinned staging buffer (double-buffered behind an event) and one
 copy to the device; per-sample (I, U) stay on the device until Evaluator.result().  The resampled pixels follow hostutil's
 restatement of skimage.transform.resize (parity-unpinned against scikit-image itself).
@@ -178,6 +184,24 @@ def mask_iu(score_map, gt_masks, thresh: float = 1e-9, want_masks: bool = False,
     return iu, [mo[d.offset: d.offset + d.h * d.w].view(d.h, d.w) for d in descs]
 
 
+def _metrics(iu: np.ndarray, thresholds: Sequence[float]) -> Dict[str, float]:
+    # hostutil.SegEval's arithmetic, in sample order
+    cum_I = cum_U = 0
+    sum_iou = 0.0
+    correct = np.zeros(len(thresholds), dtype=np.int64)
+    for I, U in iu.tolist():
+        iou = float(I) / U
+        cum_I += I
+        cum_U += U
+        sum_iou += iou
+        correct += np.array([iou >= t for t in thresholds])
+    total = len(iu)
+    out = {"precision@%s" % t: float(c) / total for t, c in zip(thresholds, correct)}
+    out["overall_IoU"] = cum_I / cum_U
+    out["mean_IoU"] = sum_iou / total
+    return out
+
+
 def _check_model(model):
     if getattr(model, "video", False):
         raise ValueError("Evaluator: the video model (CMPC_video_mm_tgraph_allvec) is not supported; its A2D evaluation is out of scope")
@@ -256,21 +280,7 @@ class Evaluator:
         self.n += n
 
     def _metrics(self, iu: np.ndarray) -> Dict[str, float]:
-        # hostutil.SegEval's arithmetic, in sample order
-        cum_I = cum_U = 0
-        sum_iou = 0.0
-        correct = np.zeros(len(self.thresholds), dtype=np.int64)
-        for I, U in iu.tolist():
-            iou = float(I) / U
-            cum_I += I
-            cum_U += U
-            sum_iou += iou
-            correct += np.array([iou >= t for t in self.thresholds])
-        total = len(iu)
-        out = {"precision@%s" % t: float(c) / total for t, c in zip(self.thresholds, correct)}
-        out["overall_IoU"] = cum_I / cum_U
-        out["mean_IoU"] = sum_iou / total
-        return out
+        return _metrics(iu, self.thresholds)
 
     def per_sample(self) -> np.ndarray:
         """(I, U) of every sample added so far (flushes the partial batch), int64 [n, 2]."""
@@ -287,3 +297,174 @@ class Evaluator:
         if self.dcrf:
             out.update({"dcrf_" + k: v for k, v in self._metrics(self.iu_crf[: self.n].cpu().numpy()).items()})
         return out
+
+
+# ---- CMPC_video_mm_tgraph_allvec on an A2D split (CMPC_video/trainval_video.py:136-291) --------------------------------------------------
+VIDEO_THRESHOLDS = (.5, .55, .6, .65, .7, .75, .8, .85, .9, .95)        # trainval_video.py:147
+VIDEO_OVERLAP = False          # VideoEvaluator(overlap=None): on one MI355X the overlap was 2-4 % slower
+
+
+def check_video_sample(i: int, text, image, frames, gt_mask, T: int, n_frames: int):
+    """add()'s validation of one A2D test sample as build_A2D_batches.py:137-143 stores it (text_batch, im_batch, frames, mask_batch).
+    Raises ValueError naming sample `i`; returns (END-padded ids int32 [1, T], seq_len int32 [1], the FRAME_IDX frames, the key image,
+    the mask as uint8 {0, 1})."""
+    from .model import FRAME_IDX, video_words
+    t = np.asarray(text)
+    if t.ndim != 1 or t.shape[0] != T or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError("sample %d: text must be integer ids [%d], got %s %s" % (i, T, t.dtype, t.shape))
+    if not np.any(t != 0):
+        raise ValueError("sample %d: the sentence holds only pad ids (the model needs at least one word)" % i)
+    try:
+        we, sl = video_words(t, HU.first_valid_idx(t), T)
+    except ValueError as e:
+        raise ValueError("sample %d: %s" % (i, e)) from None
+    fr = list(frames) if isinstance(frames, (list, tuple)) or (isinstance(frames, np.ndarray) and frames.dtype == object) else None
+    if fr is None:
+        fa = np.asarray(frames)
+        if fa.ndim != 4:
+            raise ValueError("sample %d: frames must be [%d, h, w, 3], got %s" % (i, n_frames, fa.shape))
+        fr = list(fa)
+    if len(fr) != n_frames:
+        raise ValueError("sample %d: %d frames, the model takes %d" % (i, len(fr), n_frames))
+    fr = [np.asarray(f) for f in fr]
+    for k, f in enumerate(fr):
+        if f.dtype != np.uint8:
+            raise ValueError("sample %d: frame %d is %s, expected uint8" % (i, k, f.dtype))
+        if f.shape != fr[0].shape:
+            raise ValueError("sample %d: frame %d is %s, frame 0 %s (a clip's frames share one size)" % (i, k, f.shape, fr[0].shape))
+    if fr[0].ndim != 3 or fr[0].shape[2] != 3 or fr[0].shape[0] == 0 or fr[0].shape[1] == 0:
+        raise ValueError("sample %d: frames must be [h, w, 3] with h, w > 0, got %s" % (i, fr[0].shape))
+    im = np.asarray(image)
+    if im.dtype != np.uint8:
+        raise ValueError("sample %d: the key image is %s, expected uint8" % (i, im.dtype))
+    if im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] not in (1, 3)) or im.shape[0] == 0 or im.shape[1] == 0:
+        raise ValueError("sample %d: the key image must be [h, w] or [h, w, 1|3] with h, w > 0, got %s" % (i, im.shape))
+    m = np.asarray(gt_mask)
+    if m.ndim == 3 and m.shape[2] == 1:
+        m = m[:, :, 0]
+    if m.shape != im.shape[:2]:
+        raise ValueError("sample %d: mask %s, key image %s (the mask is at the key image's size)" % (i, m.shape, im.shape[:2]))
+    m = np.ascontiguousarray(m != 0).view(np.uint8)
+    if not m.any():
+        raise ValueError("sample %d: empty mask (U would be 0; build_A2D_batches.py:98 drops these)" % i)
+    return we, sl, [np.ascontiguousarray(fr[k]) for k in FRAME_IDX], np.ascontiguousarray(im), m
+
+
+class VideoEvaluator:
+    """The video driver's `-m test` loop (trainval_video.py:186-291) on the GPU, one clip per forward pass (the graph is batch 1).
+    add(text, image, frames, gt_mask) takes one sample of build_A2D_batches.py's .npz files as it is stored: FRONT-padded ids [T], the
+    key image, the [frames, h, w, 3] uint8 clip and the mask at the key image's size.  Per clip, one pinned upload carries the 5 sampled
+    frames (plus the key image with dcrf) and the END-padded ids; one cmpc_eval_prep launch resizes them, forward_video_frames' path runs
+    the model on the device feed, cmpc_eval_mask_iu counts I and U of resize_and_crop(up >= score_thresh) at the mask's size (with dcrf,
+    also of DenseCRF on sigm with the key image's proc_im, :227-240).  (I, U) stay on the device until result() / per_sample(); nothing
+    synchronises between clips.  overlap=True enqueues clip n+1's upload, prep and backbone on the backbone stream before clip n's
+    head (off by default: DESIGN.md §13b); results are bit-identical either way."""
+
+    def __init__(self, model, thresholds: Sequence[float] = VIDEO_THRESHOLDS, dcrf: bool = False, score_thresh: float = 1e-9,
+                 overlap: bool = None):
+        if not getattr(model, "video", False):
+            raise ValueError("VideoEvaluator: expects the video model (CMPC_video_mm_tgraph_allvec); use Evaluator for the image models")
+        self.model, self.thresholds, self.dcrf, self.score_thresh = model, tuple(thresholds), bool(dcrf), float(score_thresh)
+        self.overlap = VIDEO_OVERLAP if overlap is None else bool(overlap)
+        self.T, self.H, self.W = model.num_steps, model.H, model.W
+        self.n = 0
+        self.iu = torch.zeros(64, 2, dtype=torch.int64, device=model.device)
+        self.iu_crf = torch.zeros(64, 2, dtype=torch.int64, device=model.device) if self.dcrf else None
+        self.staging = None
+        self.pending = None            # overlap: the clip whose head is enqueued by the next add() or the flush
+
+    def _grow(self, need: int):
+        if need > self.iu.shape[0]:
+            cap = max(need, 2 * self.iu.shape[0])
+            dev = self.iu.device
+            self.iu = torch.cat([self.iu, torch.zeros(cap - self.iu.shape[0], 2, dtype=torch.int64, device=dev)])
+            if self.dcrf:
+                self.iu_crf = torch.cat([self.iu_crf, torch.zeros(cap - self.iu_crf.shape[0], 2, dtype=torch.int64, device=dev)])
+
+    def _stage(self, we, sl, frames, image):
+        """One upload of [5 frames (+ key image)] ‖ ids ‖ seq_len and one cmpc_eval_prep launch over the images, on the current stream.
+        Returns (feed [5|6, H, W, 3] f32, proc_im [5|6, H, W, 3] u8, ids [1, T] i32, seq_len [1] i32), all on the device."""
+        m = self.model
+        ims = _images_u8(frames + ([image] if self.dcrf else []))
+        descs, img_bytes = plan_prep([a.shape for a in ims], self.H, self.W)
+        ids_off = img_bytes
+        sl_off = ids_off + -(-we.nbytes // _ALIGN) * _ALIGN
+        nbytes = sl_off + _ALIGN
+        offs = list(descs) + [_Offset(ids_off), _Offset(sl_off)]
+        if self.staging is None:
+            self.staging = _Staging(m.device)
+        dev = self.staging.upload(ims + [we.view(np.uint8), sl.view(np.uint8)], offs, nbytes)
+        B = len(ims)
+        proc = torch.empty(B, self.H, self.W, 3, dtype=torch.uint8, device=m.device)
+        feed = torch.empty(B, self.H, self.W, 3, dtype=torch.float32, device=m.device)
+        _lib.call("cmpc_eval_prep", dev.data_ptr(), img_bytes, descs, B, self.H, self.W, proc.data_ptr(), feed.data_ptr(),
+                  torch.cuda.current_stream(m.device).cuda_stream)
+        ids = dev[ids_off: ids_off + we.nbytes].view(torch.int32).view(1, self.T)
+        seq = dev[sl_off: sl_off + 4].view(torch.int32)
+        return feed, proc, ids, seq
+
+    def add(self, text, image, frames, gt_mask):
+        m = self.model
+        we, sl, fr, im, gt = check_video_sample(self.n, text, image, frames, gt_mask, self.T, m.frames)
+        with torch.no_grad(), torch.cuda.device(m.device):
+            main = torch.cuda.current_stream(m.device)
+            if self.overlap and m.bb_stream is not None:
+                bb = m.bb_stream
+                bb.wait_stream(main)              # the head that last read this staging slot's ids, and the taps of this backbone slot
+                with torch.cuda.stream(bb):
+                    feed, proc, ids, seq = self._stage(we, sl, fr, im)
+                    ready = torch.cuda.Event()
+                    ready.record(bb)
+                proc.record_stream(main)
+                feats, done = m.features_async(feed[:len(fr)], ready=ready)
+                clip = (feats, done, m._tap_events, ids, seq, proc, gt, self.n)
+                self._head(self.pending)
+                self.pending = clip
+            else:
+                feed, proc, ids, seq = self._stage(we, sl, fr, im)
+                feats, done = m.features_async(feed[:len(fr)])
+                self._head((feats, done, m._tap_events, ids, seq, proc, gt, self.n))
+        self.n += 1
+
+    def _head(self, clip):
+        if clip is None:
+            return
+        feats, done, tap_events, ids, seq, proc, gt, i = clip
+        m = self.model
+        m._tap_events = tap_events          # CMPC_BB_STAGED: the per-level events of THIS clip's backbone pass
+        out = m._video_fetch(feats, done, ids, seq)
+        self._grow(i + 1)
+        mask_iu(out["up"].float(), [gt], self.score_thresh, out=self.iu[i: i + 1])
+        if self.dcrf:
+            from . import crf
+            key = crf.dense_crf_mask(out["sigm"].float().reshape(self.H, self.W), proc[-1], device=m.device)
+            mask_iu(key[None], [gt], 0.5, out=self.iu_crf[i: i + 1])
+
+    def _flush(self):
+        clip, self.pending = self.pending, None
+        with torch.no_grad(), torch.cuda.device(self.model.device):
+            self._head(clip)
+
+    def per_sample(self) -> np.ndarray:
+        """(I, U) of every clip added so far, int64 [n, 2]."""
+        self._flush()
+        return self.iu[: self.n].cpu().numpy()
+
+    def result(self) -> Dict[str, float]:
+        """Evaluator.result()'s keys (precision@t for the ten thresholds, overall_IoU, mean_IoU, samples, dcrf_* with dcrf)."""
+        self._flush()
+        if self.n == 0:
+            raise ValueError("VideoEvaluator.result: no samples")
+        out = _metrics(self.iu[: self.n].cpu().numpy(), self.thresholds)
+        out["samples"] = self.n
+        if self.dcrf:
+            out.update({"dcrf_" + k: v for k, v in _metrics(self.iu_crf[: self.n].cpu().numpy(), self.thresholds).items()})
+        return out
+
+
+class _Offset:
+    """A staging entry that is not an image (the ids, the length): only its offset."""
+    __slots__ = ("offset",)
+
+    def __init__(self, offset: int):
+        self.offset = offset

@@ -5,6 +5,7 @@
                                                          '<unk>' present, e.g. data/vocabulary_Gref.txt)
   image feed            trainval_model.py:90-91,229-230,371   (RGB -> BGR, minus the channel means)
   mask IoU bookkeeping  util/eval_tools.py:31-35, trainval_model.py:267-296   (I/U, cumulative IoU, precision@X)
+  video valid_idx       CMPC_video/trainval_video.py:191-197   (first non-pad position of the front-padded ids)
 
 Resizing (util/im_processing.py:7-41) goes through scikit-image in the reference (third-party, not installed here, and its
 `resize` defaults changed between releases).  `resize_and_pad_geometry` / `resize_and_crop_geometry` return the geometry those
@@ -182,3 +183,13 @@ def end_padded(text_front_padded, pad: int = 0) -> Tuple[np.ndarray, np.ndarray]
     if a.ndim == 1:
         return ids[0], seq_len[0]
     return ids, seq_len
+
+
+def first_valid_idx(text_front_padded, pad: int = 0) -> int:
+    """The video driver's `valid_idx` (trainval_video.py:191-197): the index of the first non-pad id of a front-padded sentence [T],
+    0 when every id is a pad (the driver's loop then never assigns it)."""
+    a = np.asarray(text_front_padded)
+    if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("first_valid_idx: expected integer ids [T], got %s %s" % (a.dtype, a.shape))
+    nz = np.flatnonzero(a != pad)
+    return int(nz[0]) if nz.size else 0

@@ -39,6 +39,19 @@ MODELS = {"CMPC_model": (_lib.MODEL_CMPC, 0), "CMPCv5_BiLSTM_model": (_lib.MODEL
 FRAME_IDX = (0, 4, 8, 12, 15)                          # CMPC_video_mm_tgraph_allvec.py:70
 
 
+def video_words(words, valid_idx, T: int):
+    """The video graph drops the pad steps (vid:125-142): the same LSTM over the valid words only.  words [1, T] (or [T]) FRONT-padded
+    with valid_idx[0, 0] pad ids -> the handle's END-padded int32 ids [1, T] and int32 seq_len [1] (host arrays)."""
+    w = np.asarray(words.cpu() if torch.is_tensor(words) else words).astype(np.int64).reshape(1, T)
+    vi = int(np.asarray(valid_idx.cpu() if torch.is_tensor(valid_idx) else valid_idx).reshape(-1)[0])
+    if vi < 0 or vi >= T or np.any(w[0, :vi] != 0) or np.any(w[0, vi:] == 0):
+        raise ValueError("words must be front-padded with exactly valid_idx[0, 0] pad ids (util/text_processing.py:42-53)")
+    n = T - vi
+    we = np.zeros((1, T), dtype=np.int32)
+    we[0, :n] = w[0, vi:]
+    return we, np.array([n], dtype=np.int32)
+
+
 def tdt(dt: int):
     return {DT_F32: torch.float32, DT_BF16: torch.bfloat16, DT_F16: torch.float16}[dt]
 
@@ -385,24 +398,22 @@ class LSTM_model(object):
 
     # ---- CMPC_video_mm_tgraph_allvec: feeds words (FRONT-padded), im (unused by the graph), target_fine, valid_idx, clip (vid:62-66) -------
     def _video_feeds(self, words, valid_idx, clip):
-        """The graph drops the pad steps (vid:125-142): the same LSTM over the valid words only.  words [1, T] front-padded with
-        valid_idx[0, 0] pad words -> END-padded ids + seq_len for the handle; clip [1, frames, H, W, 3] -> the 5 sampled frames."""
-        T, H, W = self.num_steps, self.H, self.W
-        w = np.asarray(words.cpu() if torch.is_tensor(words) else words).astype(np.int64).reshape(1, T)
-        vi = int(np.asarray(valid_idx.cpu() if torch.is_tensor(valid_idx) else valid_idx).reshape(-1)[0])
-        if vi < 0 or vi >= T or np.any(w[0, :vi] != 0) or np.any(w[0, vi:] == 0):
-            raise ValueError("words must be front-padded with exactly valid_idx[0, 0] pad ids (util/text_processing.py:42-53)")
-        n = T - vi
-        we = np.zeros((1, T), dtype=np.int32)
-        we[0, :n] = w[0, vi:]
+        """The driver's feeds -> (END-padded ids, seq_len, the 5 sampled frames on the device): video_words() on words / valid_idx;
+        clip [1, frames, H, W, 3] -> tf.gather(clip, [0, 4, 8, 12, 15], axis=1) (vid:70)."""
+        we, sl = video_words(words, valid_idx, self.num_steps)
+        H, W = self.H, self.W
         if tuple(clip.shape) != (1, self.frames, H, W, 3):
             raise ValueError(f"clip must be [1,{self.frames},{H},{W},3], got {tuple(clip.shape)}")
-        fr = self._dev(clip, torch.float32)[0, list(FRAME_IDX)].contiguous()           # tf.gather(clip, [0, 4, 8, 12, 15], axis=1) (vid:70)
-        return torch.from_numpy(we), torch.tensor([n], dtype=torch.int32), fr
+        fr = self._dev(clip, torch.float32)[0, list(FRAME_IDX)].contiguous()
+        return torch.from_numpy(we), torch.from_numpy(sl), fr
 
     def head_video(self, feats, words_end, seq_len, target=None, after=None):
         """build_graph() (vid:91-187) on the taps of the 5 sampled frames, feats = (c3, c4, c5) each [5, h, w, .]."""
         return self.head(feats, words_end, seq_len, target, after=after)
+
+    def _video_fetch(self, feats, ev, words_end, seq_len):
+        o = self.head(feats, words_end, seq_len, after=ev)
+        return {"pred": o["pred"].clone(), "up": o["up"].clone(), "sigm": o["sigm"].clone()}
 
     @torch.no_grad()
     def forward_video(self, words, im, valid_idx, clip):
@@ -410,8 +421,26 @@ class LSTM_model(object):
         with torch.cuda.device(self.device):
             we, sl, fr = self._video_feeds(words, valid_idx, clip)
             feats, ev = self.features_async(fr)
-            o = self.head(feats, we, sl, after=ev)
-            return {"pred": o["pred"].clone(), "up": o["up"].clone(), "sigm": o["sigm"].clone()}
+            return self._video_fetch(feats, ev, we, sl)
+
+    def _check_video_frames(self, frames):
+        if not self.video:
+            raise ValueError("forward_video_frames: %s is not the video model" % self.model_name)
+        want = (len(FRAME_IDX), self.H, self.W, 3)
+        if not torch.is_tensor(frames) or frames.device != self.device or frames.dtype != torch.float32 or tuple(frames.shape) != want:
+            raise ValueError("frames must be a float32 %s tensor on %s (the sampled frames, BGR - mu), got %s" % (
+                list(want), self.device, (frames.dtype, tuple(frames.shape), str(frames.device)) if torch.is_tensor(frames) else type(frames)))
+
+    @torch.no_grad()
+    def forward_video_frames(self, words, valid_idx, frames):
+        """forward_video on a device feed: `frames` = the clip's sampled frames (FRAME_IDX), already gathered and prepared, a float32
+        [5, H, W, 3] tensor on the model's device.  Returns exactly what forward_video returns for a clip whose frames FRAME_IDX are
+        `frames`; only the ids and the length cross from the host."""
+        self._check_video_frames(frames)
+        with torch.cuda.device(self.device):
+            we, sl = video_words(words, valid_idx, self.num_steps)
+            feats, ev = self.features_async(frames.contiguous())
+            return self._video_fetch(feats, ev, torch.from_numpy(we), torch.from_numpy(sl))
 
     def train_step_video(self, words, im, target_fine, valid_idx, clip):
         """sess.run([train_step, cls_loss, learning_rate, pred, target], feed) (trainval_video.py:93-101)."""
