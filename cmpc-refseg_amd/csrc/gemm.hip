@@ -1421,11 +1421,14 @@ extern "C" int cmpc_conv_nhwc(const cmpc_conv_args* a, void* stream) {
 }
 
 
-static int tn_validate(const cmpc_gemm_tn_args* a) {
+// grouped: cmpc_gemm_tn_grouped expands an outer batch that shares one output (nb2 > 1, o_bs == 0) into single products, so it takes any
+// nb there; cmpc_gemm_tn folds all of its slabs into ONE region and needs nb == 1
+static int tn_validate(const cmpc_gemm_tn_args* a, bool grouped) {
     if (!a || a->R < 0 || a->Kv <= 0 || a->Nv <= 0 || a->nb < 1 || a->nb > 8 || a->nb2 < 1) {
         cmpc_set_error("gemm_tn: bad args"); return CMPC_EINVAL;
     }
     if (a->dtype != DT_F32 && a->dtype != DT_BF16 && a->dtype != DT_F16) { cmpc_set_error("gemm_tn: bad dtype"); return CMPC_EINVAL; }
+    if (!grouped && a->nb2 > 1 && a->o_bs == 0 && a->nb != 1) { cmpc_set_error("gemm_tn: o_bs == 0 needs nb == 1"); return CMPC_EINVAL; }
     if (a->R == 0) return CMPC_OK;
     if (!a->A || !a->D || !a->out) { cmpc_set_error("gemm_tn: null operand"); return CMPC_EINVAL; }
     const int esz = a->dtype == DT_F32 ? 4 : 2;
@@ -1463,7 +1466,7 @@ int cmpc_gemm_tn_grouped_cached(const void* args_, int n, void* const* tables_de
     // 1. expand: an outer batch that accumulates into ONE output (o_bs == 0) becomes a chain of single products
     std::vector<cmpc_gemm_tn_args> ex;
     for (int i = 0; i < n; ++i) {
-        const int rc = tn_validate(&args[i]);
+        const int rc = tn_validate(&args[i], true);
         if (rc != CMPC_OK) return rc;
         if (args[i].R == 0) continue;
         if (args[i].nb2 > 1 && args[i].o_bs == 0) {
@@ -1666,7 +1669,7 @@ extern "C" int cmpc_gemm_tn_grouped(const cmpc_gemm_tn_args* args, int n, void* 
 }
 
 extern "C" int cmpc_gemm_tn(const cmpc_gemm_tn_args* a, void* stream) {
-    const int rc = tn_validate(a);
+    const int rc = tn_validate(a, false);
     if (rc != CMPC_OK) return rc;
     if (a->rsplit < 1) { cmpc_set_error("gemm_tn: rsplit must be >= 1"); return CMPC_EINVAL; }
     if (a->R == 0) return CMPC_OK;              // empty reduction: out += 0
@@ -1687,13 +1690,8 @@ extern "C" int cmpc_gemm_tn(const cmpc_gemm_tn_args* a, void* stream) {
     if (slabs) {
         if (cmpc_check_launch("gemm_tn") != CMPC_OK) return CMPC_EHIP;
         if (shared_out) {      // every (b2, split) slab of inner entry b1 folds into the one shared region
-            for (int b1 = 0; b1 < a->nb; ++b1) {
-                // slabs are ordered [bz = b1 + nb * b2][by]: for nb == 1 the nb2 * rsplit slabs are contiguous
-                if (a->nb != 1) { cmpc_set_error("gemm_tn: o_bs == 0 needs nb == 1"); return CMPC_EINVAL; }
-                const int rc = cmpc_reduce_parts_f32(slabs, slab_size, 1, a->rsplit * a->nb2, a->Kv, lds, a->Nv, a->out + a->o_off[0], 0, a->ldo, 1, st);
-                if (rc != CMPC_OK) return rc;
-            }
-            return CMPC_OK;
+            // slabs are ordered [bz = b1 + nb * b2][by]: with nb == 1 (tn_validate) the nb2 * rsplit slabs are contiguous
+            return cmpc_reduce_parts_f32(slabs, slab_size, 1, a->rsplit * a->nb2, a->Kv, lds, a->Nv, a->out + a->o_off[0], 0, a->ldo, 1, st);
         }
         return tn_fold(*a, a->rsplit, slabs, slab_size, lds, st);
     }

@@ -638,8 +638,9 @@ extern "C" int cmpc_lowrank_nn(int dt, const void* A, int lda, int64_t sA, const
     const dim3 grid((M + per - 1) / per, batch);
 #define LR_LAUNCH(TT, KC) hipLaunchKernelGGL((lowrank_nn_kernel<TT, KC>), grid, dim3(256), 0, ST, (const TT*)A, lda, (long)sA, (const TT*)Bk, ldb, (long)sB, \
                                              (TT*)C, ldc, (long)sC, M, N, n_valid, Kv, alpha, accumulate, per)
-    if (dt == DT_F16) { if (kc <= 2) LR_LAUNCH(f16_t, 2); else LR_LAUNCH(f16_t, 3); }
-    else { if (kc <= 2) LR_LAUNCH(bf16_t, 2); else LR_LAUNCH(bf16_t, 3); }
+    // KC = kc exactly: a row of A is read in KC 16-B chunks, and only 8 * kc columns of it are guaranteed to exist (lda >= 8 * kc)
+    if (dt == DT_F16) { if (kc == 1) LR_LAUNCH(f16_t, 1); else if (kc == 2) LR_LAUNCH(f16_t, 2); else LR_LAUNCH(f16_t, 3); }
+    else { if (kc == 1) LR_LAUNCH(bf16_t, 1); else if (kc == 2) LR_LAUNCH(bf16_t, 2); else LR_LAUNCH(bf16_t, 3); }
 #undef LR_LAUNCH
     return cmpc_check_launch("lowrank_nn");
 }

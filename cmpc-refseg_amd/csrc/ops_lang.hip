@@ -610,6 +610,7 @@ extern "C" int cmpc_pack_weights(const float* master, void* arena, const cmpc_pa
 extern "C" int cmpc_adam_step(float* params, const float* grads, float* m, float* v, const cmpc_adam_seg* segs_dev, int nseg,
                               float lr_t, float beta1, float beta2, float eps, float gscale, int* nonfinite, void* stream) {
     if (nseg <= 0) return CMPC_OK;
+    if (!params || !grads || !m || !v || !segs_dev) { cmpc_set_error("adam_step: params, grads, m, v and segs are required"); return CMPC_EINVAL; }
     hipLaunchKernelGGL(adam_kernel, dim3(nseg), dim3(256), 0, ST, params, grads, m, v, segs_dev, lr_t, beta1, beta2, eps, gscale, nonfinite);
     return cmpc_check_launch("adam_step");
 }

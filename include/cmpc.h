@@ -64,7 +64,7 @@ typedef struct {
     float* out; int ldo;                /* out[k, n] += alpha * sum_r A[r,k] D[r,n]  (one writer per element; split reductions go through slabs folded in a fixed order) */
     int R, Kv, Nv;                      /* reduction length, valid output rows / cols */
     int nb; int64_t a_off[8], d_off[8], o_off[8];  /* inner batch: element offsets */
-    int nb2; int64_t a_bs, d_bs, o_bs;  /* outer batch: strides */
+    int nb2; int64_t a_bs, d_bs, o_bs;  /* outer batch: strides; o_bs == 0 sums every outer entry into one output (cmpc_gemm_tn: needs nb == 1) */
     int rsplit;                         /* workgroups along the reduction */
     float alpha;
     const void* zeros;                  /* optional: >= 256 B of device zeros (enables the LDS-DMA pipeline for bf16) */
@@ -88,8 +88,8 @@ typedef struct {
     const void* X; int ldx;
     const void* Wt; int ldw;
     const float* bias;
-    const void* res;            /* optional residual added before the ReLU */
-    void* Y; int ldy;
+    const void* res;            /* optional residual added before the ReLU; read with Y's row stride ldy */
+    void* Y; int ldy;           /* columns [Cout, ldy) of Y are not written */
     int B, H, W, Cin, Cout, ksize, stride, dil, relu;
     const void* zeros;
 } cmpc_conv_args;

@@ -130,6 +130,58 @@ def sum_atol(terms, dim):
     return 1e-7 * terms.abs().sum(dim)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# products (gemm_nt / gemm_tn / conv_nhwc / lowrank_nn)
+# ---------------------------------------------------------------------------------------------------------------------------
+U24 = 2.0 ** -24
+# fp32 accumulation of a K-term product: one rounding of at most 2^-24 |partial sum| per accumulator update (K/32 .. K/4 MFMA steps, K/1024
+# per lane in the skinny kernel, plus the fp32 products' own rounding in fp32 mode).  The partial sums of a random-signed reduction stay near
+# ||(a_k b_k)||_2 and the roundings are independent, so their sum grows as sqrt(updates) <= sqrt(K); C_ACC = 8 covers the partial sums'
+# excursions above the 2-norm.  A one-sided reduction (all terms of one sign) is not bounded by this and is not used.
+C_ACC = 8.0
+# cmpc_tanh (cmpc_common.h): the bound documented there, which test_gpu_ops_gemm's tanh sweep checks over every float32 with |x| in [2^-12, 16)
+TANH_ABS, TANH_REL = 1.2e-7, 1e-6
+
+
+def prod_norm(A, B):
+    """||(a_mk b_nk)_k||_2 for every (m, n): sqrt((A o A) (B o B)^T) in float64; A [..., M, K], B [..., N, K]"""
+    A, B = A.double(), B.double()
+    return torch.sqrt((A * A) @ (B * B).transpose(-1, -2))
+
+
+def acc_atol(norm, K, alpha=1.0):
+    """the fp32-accumulation term of a product element: C_ACC 2^-24 sqrt(K) |alpha| ||(a_k b_k)||_2"""
+    return C_ACC * U24 * math.sqrt(max(K, 1)) * abs(alpha) * norm
+
+
+def epi_atol(pre_mag, act=0, y=None, c0=None):
+    """epilogue term: the fp32 evaluation of alpha acc + bias + sbias + pbias (a rounding per operation over the magnitude pre_mag = |alpha
+    acc| + |bias| + |sbias| + |pbias| it passes through; every activation is 1-Lipschitz, so that error carries through), the activation's
+    own error at its float64 output y (relu exact, tanh as documented for cmpc_tanh, sigmoid: expf and a division) and the accumulate add
+    of c0"""
+    e = 4 * U24 * pre_mag
+    if act == 2:
+        e = e + TANH_ABS + TANH_REL * y.abs()
+    elif act == 3:
+        e = e + 4 * U24
+    if c0 is not None:
+        e = e + U24 * ((y.abs() if y is not None else 0) + c0.abs())
+    return e
+
+
+def assert_prod(got, ref, dt_out, K, norm, alpha=1.0, epi=0.0, what="", old_tol=None):
+    """|got - ref| <= u_out |ref| + C_ACC 2^-24 sqrt(K) |alpha| ||(a_k b_k)||_2 + epi on every element (u_out: one ulp of a 16-bit output, 0
+    for fp32).  old_tol: the whole-tensor bound an older test (U.rel_err: max |err| / max |ref|) puts on the same product -- this bound
+    must be at least as strict there, which is asserted on the reference itself."""
+    ref = ref.detach().double().cpu()
+    atol = acc_atol(norm.detach().double().cpu(), K, alpha) + (epi.detach().double().cpu() if torch.is_tensor(epi) else epi)
+    if old_tol is not None and ref.numel():
+        mx = float(ref.abs().max())
+        worst = float((1e-7 * mx + SUBNORMAL.get(dt_out, 0.0) + atol + ULP[dt_out] * ref.abs()).max())
+        assert worst <= old_tol * mx, f"{what}: per-element bound {worst / mx:.3g} of max|ref| is looser than the old {old_tol:g}"
+    assert_close(got, ref, dt_out, K=K, what=what, rtol=ULP[dt_out], atol=atol)
+
+
 def assert_zero(t, what=""):
     t = t.detach().cpu()
     assert bool((t == 0).all()), f"{what}: pad elements not written as 0 ({int((t != 0).sum())} non-zero)"

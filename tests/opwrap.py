@@ -104,9 +104,10 @@ def lowrank_nn(dt, A, lda, sA, Bk, ldb, sB, C, ldc, sC, M, N, Kv, n_valid=None, 
 
 
 def gemm_tn(dt, A, lda, Ka, D, ldd, Nd, out, ldo, R, Kv, Nv, offs=((0, 0, 0),), nb2=1, a_bs=0, d_bs=0, o_bs=0,
-            alpha=1.0, rsplit=None, wg=None):
+            alpha=1.0, rsplit=None, wg=None, conv=None):
     """out[k, n] += alpha * sum_r A[r, k] D[r, n]; offs: (a_off, d_off, o_off) per inner batch (elements).
-    wg: an object with a `deferred` list -> the product is appended there (args, A, D) for one cmpc_gemm_tn_grouped launch."""
+    wg: an object with a `deferred` list -> the product is appended there (args, A, D) for one cmpc_gemm_tn_grouped launch.
+    conv: (H, W, dy, dx) -> one tap of a convolution's weight gradient (rows are pixels of [*, H, W] maps, A read at (y + dy, x + dx))."""
     if wg is not None:
         wg = wg.deferred
     a = GemmTnArgs()
@@ -125,10 +126,52 @@ def gemm_tn(dt, A, lda, Ka, D, ldd, Nd, out, ldo, R, Kv, Nv, offs=((0, 0, 0),), 
         rsplit = max(1, min((R + 4 * br - 1) // (4 * br), (512 + tiles - 1) // tiles))
     a.rsplit, a.alpha = rsplit, alpha
     a.zeros = _zero_page(A.device if torch.is_tensor(A) else torch.device('cuda', torch.cuda.current_device()))
+    if conv is not None:
+        a.conv_H, a.conv_W, a.conv_dy, a.conv_dx = conv
     if isinstance(wg, list):
         wg.append((a, A, D))         # operands stay referenced (hence allocated and unmodified) until the flush
         return
     _lib.call("cmpc_gemm_tn", ctypes.byref(a), _st())
+
+
+def gemm_tn_grouped(items):
+    """items: the (args, A, D) list gemm_tn(..., wg=) collected -> one cmpc_gemm_tn_grouped call"""
+    arr = (GemmTnArgs * len(items))()
+    for i, (a, _A, _D) in enumerate(items):
+        ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(a), ctypes.sizeof(GemmTnArgs))
+    _lib.call("cmpc_gemm_tn_grouped", arr, len(items), _st())
+
+
+def conv_nhwc(dt, X, ldx, Wt, ldw, bias, Y, ldy, B, H, W, Cin, Cout, ksize, stride=1, dil=1, relu=False, res=None):
+    """Y[B, Ho, Wo, :Cout] = relu?(conv_SAME(X, Wt) + bias (+ res)): cmpc_conv_nhwc; res is read with row stride ldy"""
+    a = _lib.ConvArgs()
+    a.dtype = dt
+    a.X, a.ldx, a.Wt, a.ldw = _p(X), ldx, _p(Wt), ldw
+    a.bias, a.res, a.Y, a.ldy = _p(bias), _p(res), _p(Y), ldy
+    a.B, a.H, a.W, a.Cin, a.Cout, a.ksize, a.stride, a.dil, a.relu = B, H, W, Cin, Cout, ksize, stride, dil, int(relu)
+    a.zeros = _zero_page(X.device)
+    _lib.call("cmpc_conv_nhwc", ctypes.byref(a), _st())
+
+
+class LaunchTrace:
+    """with LaunchTrace() as t: ...  -> t.names: the launch names (cmpc_check_launch) recorded on the current stream, in first-seen order;
+    t.counts: launches per name"""
+
+    def __enter__(self):
+        _lib.call("cmpc_launch_trace", 1, _st())
+        self.names, self.counts = [], {}
+        return self
+
+    def __exit__(self, *exc):
+        lib = _lib.load()
+        name, ms, n = ctypes.c_char_p(), ctypes.c_double(), ctypes.c_int64()
+        i = 0
+        while lib.cmpc_launch_trace_read(i, ctypes.byref(name), ctypes.byref(ms), ctypes.byref(n)) == 0:
+            self.names.append(name.value.decode())
+            self.counts[self.names[-1]] = n.value
+            i += 1
+        _lib.call("cmpc_launch_trace", 0, None)
+        return False
 
 
 _ZERO_PAGES = {}

@@ -8,7 +8,7 @@ stage actually STORED (16-bit included), so 1-ulp tolerances stay meaningful; on
 
 Tolerance terms beyond opref.assert_close's (each stated where it is used) come from `mag`, the float64 magnitude an output's error scales
 with: the sum of |terms| a float32 evaluation passes through.  The gate functions are sigmoid_fast (|error| < 2e-7) and cmpc_tanh
-(|error| < 1e-7 absolute), cmpc_common.h; both are absolute errors on values in (-1, 1), so they enter as a multiple of the magnitude."""
+(|error| < 1.2e-7 absolute), cmpc_common.h; both are absolute errors on values in (-1, 1), so they enter as a multiple of the magnitude."""
 import math
 
 import pytest
@@ -24,7 +24,7 @@ EPS = 1e-12
 # 4 x the 512-row cap of the peephole gradients); a small map; N = 1 with B = 8; M == ld
 SHAPES = [(2, 1600, 500, 512), (1, 4096, 1000, 1024), (3, 7, 24, 64), (8, 1, 8, 64), (1, 257, 512, 512)]
 # float32 evaluation of a gate expression: one rounding (6e-8) per operation over a few operations, plus the sigmoid_fast / cmpc_tanh
-# errors (2e-7, 1e-7) -- 4e-7 of the magnitude the expression passes through
+# errors (2e-7, 1.2e-7) -- 4e-7 of the magnitude the expression passes through
 U_F32 = 4e-7
 
 

@@ -152,3 +152,108 @@ def test_decoder_limits(lib):
         _rejects(lib, "cmpc_conv_to1_fwd", 0, P, ld, P, P, P, R, C, None, msg="conv_to1_fwd")
         _rejects(lib, "cmpc_conv_to1_bwd", 0, P, P, ld, P, P, P, P, R, C, None, msg="conv_to1_bwd")
     _rejects(lib, "cmpc_conv_to1_bwd", 1, P, P, 2056, P, P, P, P, 10, 2050, None, msg="conv_to1_bwd")
+
+
+# ---- the contraction entry points (csrc/gemm.hip, csrc/ops_fusion.hip lowrank_nn, csrc/ops_lang.hip adam_step) ----------------------
+def _nt(dt=1, M=64, N=64, Ks=(64,), lda=None, ldb=None, ldc=64, batch=1, C=P):
+    a = L.GemmNtArgs()
+    a.dtype, a.nseg = dt, len(Ks)
+    for i, K in enumerate(Ks[:3]):
+        a.A[i], a.Bt[i], a.K[i] = P, P, K
+        a.lda[i], a.ldb[i] = lda if lda is not None else K, ldb if ldb is not None else K
+    a.C, a.ldc, a.M, a.N, a.n_valid, a.batch, a.alpha = C, ldc, M, N, N, batch, 1.0
+    return a
+
+
+def test_gemm_nt_limits(lib):
+    import ctypes
+    good = _nt()
+    bad = [_nt(Ks=()), _nt(M=0), _nt(N=0), _nt(batch=0), _nt(dt=3), _nt(dt=-1),
+           _nt(Ks=(40,)), _nt(dt=0, Ks=(48,)),                      # K a multiple of 64 (16-bit) / 32 (fp32)
+           _nt(lda=68), _nt(ldb=66), _nt(dt=0, Ks=(32,), lda=34),   # 16-B aligned rows
+           _nt(N=66, ldc=72), _nt(ldc=66), _nt(C=None)]
+    four = _nt(Ks=(64, 64, 64))
+    four.nseg = 4
+    bad.append(four)
+    nullA = _nt()
+    nullA.A[0] = None
+    bad.append(nullA)
+    for a in bad:
+        _rejects(lib, "cmpc_gemm_nt", ctypes.byref(a), None, msg="gemm_nt")
+        _rejects(lib, "cmpc_gemm_nt_pair", ctypes.byref(good), ctypes.byref(a), None, msg="gemm_nt")
+        _rejects(lib, "cmpc_gemm_nt_pair", ctypes.byref(a), ctypes.byref(good), None, msg="gemm_nt")
+    _rejects(lib, "cmpc_gemm_nt", ctypes.byref(_nt(Ks=(40,))), None, msg="multiple of 64")
+
+
+def _tn(dt=1, R=100, Kv=64, Nv=64, lda=64, ldd=64, Ka=64, Nd=64, nb=1, nb2=1, o_bs=64 * 64, rsplit=1):
+    a = L.GemmTnArgs()
+    a.dtype, a.A, a.lda, a.Ka, a.D, a.ldd, a.Nd, a.out, a.ldo = dt, P, lda, Ka, P, ldd, Nd, P, 64
+    a.R, a.Kv, a.Nv, a.nb, a.nb2, a.a_bs, a.d_bs, a.o_bs, a.rsplit, a.alpha = R, Kv, Nv, nb, nb2, 64 * R, 64 * R, o_bs, rsplit, 1.0
+    return a
+
+
+def test_gemm_tn_limits(lib):
+    import ctypes
+    bad = [_tn(R=-1), _tn(Kv=0), _tn(Nv=0), _tn(nb=0), _tn(nb=9), _tn(nb2=0), _tn(dt=3),
+           _tn(lda=66), _tn(ldd=60 + 2), _tn(Ka=60 + 2), _tn(Nd=66), _tn(dt=0, lda=66)]
+    null = _tn()
+    null.out = None
+    bad.append(null)
+    off = _tn(nb=2)
+    off.a_off[1] = 4                                             # 8 B: not 16-B aligned in bf16
+    bad.append(off)
+    bs = _tn(nb2=2)
+    bs.a_bs = 68 * 100 + 4
+    bad.append(bs)
+    for a in bad:
+        _rejects(lib, "cmpc_gemm_tn", ctypes.byref(a), None, msg="gemm_tn")
+        arr = (L.GemmTnArgs * 2)(_tn(), a)
+        _rejects(lib, "cmpc_gemm_tn_grouped", arr, 2, None, msg="gemm_tn")
+    _rejects(lib, "cmpc_gemm_tn", ctypes.byref(_tn(rsplit=0)), None, msg="rsplit")
+    # an outer batch into one shared output (o_bs == 0) folds every slab into ONE region: cmpc_gemm_tn needs nb == 1 and says so
+    # before launching anything; the grouped form expands such a batch into single products and takes it
+    _rejects(lib, "cmpc_gemm_tn", ctypes.byref(_tn(nb=2, nb2=3, o_bs=0)), None, msg="o_bs == 0 needs nb == 1")
+    _rejects(lib, "cmpc_gemm_tn", ctypes.byref(_tn(nb=2, nb2=3, o_bs=0, R=0)), None, msg="o_bs == 0 needs nb == 1")
+
+
+def _conv(dt=1, k=3, s=1, dil=1, Cin=64, Cout=64, ldx=64, ldw=576, ldy=64, res=None, B=2, H=8, W=8):
+    a = L.ConvArgs()
+    a.dtype, a.X, a.ldx, a.Wt, a.ldw, a.bias, a.res, a.Y, a.ldy = dt, P, ldx, P, ldw, P, res, P, ldy
+    a.B, a.H, a.W, a.Cin, a.Cout, a.ksize, a.stride, a.dil, a.relu, a.zeros = B, H, W, Cin, Cout, k, s, dil, 1, P
+    return a
+
+
+def test_conv_nhwc_limits(lib):
+    import ctypes
+    bad = [_conv(k=2), _conv(k=5), _conv(s=3), _conv(s=0), _conv(dil=0), _conv(Cin=32), _conv(dt=0, Cin=48), _conv(Cout=12),
+           _conv(ldx=68), _conv(ldw=580), _conv(ldy=68), _conv(res=P, ldy=68), _conv(B=0), _conv(H=0), _conv(W=0)]
+    for field in ("X", "Wt", "Y", "bias", "zeros"):
+        a = _conv()
+        setattr(a, field, None)
+        bad.append(a)
+    for a in bad:
+        _rejects(lib, "cmpc_conv_nhwc", ctypes.byref(a), None, msg="conv_nhwc")
+    _rejects(lib, "cmpc_conv_nhwc", ctypes.byref(_conv(dt=3)), None, msg="dtype")
+
+
+def test_lowrank_nn_limits(lib):
+    # (dt, lda, sA, ldb, sB, ldc, sC, M, N, n_valid, Kv, batch)
+    ok = (1, 24, 24 * 10, 64, 24 * 64, 64, 640, 10, 64, 64, 20, 2)
+    for i, v in ((0, 0), (0, 3), (8, 60), (8, 2048), (8, 0), (7, 0), (10, 25), (10, 0), (11, 0),     # dtype; N = 4 * 2^j <= 1024; Kv; M; batch
+                 (1, 16), (1, 28), (3, 60), (3, 66), (5, 66), (2, 244), (4, 66), (6, 642)):         # lda >= 8 ceil(Kv / 8), % 8; ldb >= N; strides
+        a = list(ok)
+        a[i] = v
+        dt, lda, sA, ldb, sB, ldc, sC, M, N, nv, Kv, B = a
+        _rejects(lib, "cmpc_lowrank_nn", dt, P, lda, sA, P, ldb, sB, P, ldc, sC, M, N, nv, Kv, B, 1.0, 0, None, msg="lowrank_nn")
+    dt, lda, sA, ldb, sB, ldc, sC, M, N, nv, Kv, B = ok
+    for A, Bk, C in ((None, 16, 16), (16, None, 16), (16, 16, None), (8, 16, 16), (16, 12, 16), (16, 16, 4)):    # NULL / misaligned
+        _rejects(lib, "cmpc_lowrank_nn", dt, A, lda, sA, Bk, ldb, sB, C, ldc, sC, M, N, nv, Kv, B, 1.0, 0, None, msg="lowrank_nn")
+
+
+def test_adam_limits(lib):
+    for i in range(5):
+        bufs = [16, 16, 16, 16, 16]
+        bufs[i] = None
+        p, g, m, v, segs = bufs
+        _rejects(lib, "cmpc_adam_step", p, g, m, v, segs, 3, 1e-3, 0.9, 0.999, 1e-8, 1.0, None, None, msg="adam_step")
+    assert lib.cmpc_adam_step(None, None, None, None, None, 0, 1e-3, 0.9, 0.999, 1e-8, 1.0, None, None) == 0     # nothing to do
