@@ -232,6 +232,7 @@ SIGNATURES = {
     "cmpc_phase_marks_read": [_P, _I, C.POINTER(C.c_char_p), C.POINTER(C.c_float)],
     "cmpc_set_lanes": [_P, _I],
     "cmpc_dense_crf": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P],
+    "cmpc_dense_crf_lattice": [_P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P],
     "cmpc_eval_prep": [_P, _L, C.POINTER(EvalDesc), _I, _I, _I, _P, _P, _P],
     "cmpc_eval_mask_iu": [_P, _I, _I, _I, _I, _F, _P, _L, C.POINTER(EvalDesc), _P, _P, _P],
     "cmpc_launch_trace": [_I, _P],

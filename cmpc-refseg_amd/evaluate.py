@@ -227,16 +227,25 @@ def predict_masks(model, ids, seq_len, images) -> List[np.ndarray]:
     return [mk.cpu().numpy() for mk in masks]
 
 
+def _check_dcrf_method(method: str) -> str:
+    if method not in ("exact", "lattice"):
+        raise ValueError("dcrf_method must be 'exact' or 'lattice', got %r" % (method,))
+    return method
+
+
 class Evaluator:
     """The `-m test` loop (trainval_model.py:198-303) batched on the GPU.  add() queues one sample (end-padded ids [T], seq_len,
     original-size uint8 image, original-size mask); a batch of model.batch_size samples runs prep -> forward -> mask_iu (and with
     dcrf, DenseCRF on each sample's sigm / proc_im -> mask_iu on the argmax).  result() flushes a partial last batch (padded by
     repeating a sample; pads are never counted) and returns hostutil.SegEval.result()'s keys plus `samples` (and `dcrf_`-prefixed
-    metrics with dcrf)."""
+    metrics with dcrf).  dcrf_method: "exact" (one cmpc_dense_crf call per sample) or "lattice" (the batch's masks from one
+    cmpc_dense_crf_lattice call, crf.py)."""
 
-    def __init__(self, model, thresholds: Sequence[float] = (.5, .6, .7, .8, .9), dcrf: bool = False, score_thresh: float = 1e-9):
+    def __init__(self, model, thresholds: Sequence[float] = (.5, .6, .7, .8, .9), dcrf: bool = False, score_thresh: float = 1e-9,
+                 dcrf_method: str = "exact"):
         _check_model(model)
         self.model, self.thresholds, self.dcrf, self.score_thresh = model, tuple(thresholds), bool(dcrf), float(score_thresh)
+        self.dcrf_method = _check_dcrf_method(dcrf_method)
         self.B, self.H, self.W = model.batch_size, model.H, model.W
         if self.B > MAX_BATCH:
             raise ValueError("Evaluator: model.batch_size %d > %d" % (self.B, MAX_BATCH))
@@ -275,7 +284,10 @@ class Evaluator:
             if self.dcrf:
                 from . import crf
                 sigm = out["sigm"].float()
-                crf_masks = torch.stack([crf.dense_crf_mask(sigm[b].reshape(self.H, self.W), proc[b], device=m.device) for b in range(n)])
+                if self.dcrf_method == "lattice":
+                    crf_masks = crf.dense_crf_batch(sigm[:n].reshape(n, self.H, self.W), proc[:n], device=m.device, method="lattice")
+                else:
+                    crf_masks = torch.stack([crf.dense_crf_mask(sigm[b].reshape(self.H, self.W), proc[b], device=m.device) for b in range(n)])
                 mask_iu(crf_masks, gts, 0.5, out=self.iu_crf[self.n: self.n + n])
         self.n += n
 
@@ -358,13 +370,15 @@ class VideoEvaluator:
     the model on the device feed, cmpc_eval_mask_iu counts I and U of resize_and_crop(up >= score_thresh) at the mask's size (with dcrf,
     also of DenseCRF on sigm with the key image's proc_im, :227-240).  (I, U) stay on the device until result() / per_sample(); nothing
     synchronises between clips.  overlap=True enqueues clip n+1's upload, prep and backbone on the backbone stream before clip n's
-    head (off by default: DESIGN.md §13b); results are bit-identical either way."""
+    head (off by default: DESIGN.md §13b); results are bit-identical either way.  dcrf_method as in Evaluator (one key image per
+    clip: one call either way)."""
 
     def __init__(self, model, thresholds: Sequence[float] = VIDEO_THRESHOLDS, dcrf: bool = False, score_thresh: float = 1e-9,
-                 overlap: bool = None):
+                 overlap: bool = None, dcrf_method: str = "exact"):
         if not getattr(model, "video", False):
             raise ValueError("VideoEvaluator: expects the video model (CMPC_video_mm_tgraph_allvec); use Evaluator for the image models")
         self.model, self.thresholds, self.dcrf, self.score_thresh = model, tuple(thresholds), bool(dcrf), float(score_thresh)
+        self.dcrf_method = _check_dcrf_method(dcrf_method)
         self.overlap = VIDEO_OVERLAP if overlap is None else bool(overlap)
         self.T, self.H, self.W = model.num_steps, model.H, model.W
         self.n = 0
@@ -437,7 +451,7 @@ class VideoEvaluator:
         mask_iu(out["up"].float(), [gt], self.score_thresh, out=self.iu[i: i + 1])
         if self.dcrf:
             from . import crf
-            key = crf.dense_crf_mask(out["sigm"].float().reshape(self.H, self.W), proc[-1], device=m.device)
+            key = crf.dense_crf_mask(out["sigm"].float().reshape(self.H, self.W), proc[-1], device=m.device, method=self.dcrf_method)
             mask_iu(key[None], [gt], 0.5, out=self.iu_crf[i: i + 1])
 
     def _flush(self):

@@ -516,11 +516,20 @@ int cmpc_launch_count(cmpc_handle h, int64_t* n);
 /* ---- Dense CRF post-processing of the evaluation script (test.py:309-322: pydensecrf DenseCRF2D(W, H, 2), unary -log(1-p) / -log(p),
  *      addPairwiseGaussian(sxy, compat), addPairwiseBilateral(sxy, srgb, rgbim, compat), inference(iters), argmax).  sigm [H*W] fp32
  *      probabilities and rgb [H*W*3] uint8 are device pointers; q_out [2][H*W] fp32 (label 0, label 1) and / or mask_out [H*W] uint8
- *      receive the result.  The Gaussian kernels are evaluated exactly inside a 4-sigma window where the library filters through a
- *      permutohedral lattice: same recursion and normalisation, parity-unpinned against the library (not installed, not in the
- *      reference tree) ------------------------------------------------------------------------------------------------------ */
+ *      receive the result.  cmpc_dense_crf evaluates the Gaussian kernels exactly inside a 4-sigma window (the default of crf.py);
+ *      cmpc_dense_crf_lattice filters through a permutohedral lattice as the library does.  Same recursion and normalisation,
+ *      parity-unpinned against the library (not installed, not in the reference tree) ------------------------------------------- */
 int cmpc_dense_crf(const float* sigm, const unsigned char* rgb, int H, int W, float sxy_g, float compat_g, float sxy_b, float srgb,
                    float compat_b, int iters, float* q_out, unsigned char* mask_out, void* stream);
+/* The same CRF with both pairwise terms filtered through a permutohedral lattice, as pydensecrf does it (Adams, Baek & Davis 2010:
+ * O(N (d+1)) per filter, d = 2 Gaussian / d = 5 bilateral), batched: sigm [B][H*W] fp32, rgb [B][H*W*3] uint8, q_out [B][2][H*W] fp32
+ * and / or mask_out [B][H*W] uint8, all device pointers.  Every launch covers the B samples; no host synchronisation, scratch from the
+ * stream's workspace; bit-identical reruns, and a sample's result does not depend on the batch around it.  Parameters whose lattice keys
+ * leave the packing range (12 bits per bilateral coordinate) get CMPC_EINVAL naming the limit.  A failure found on the device (a hash
+ * probe loop exhausted, impossible with the table sizing) poisons that call's outputs (Q NaN, mask 255) and makes the NEXT call return
+ * CMPC_EHIP.  Parity-unpinned against pydensecrf (not installed); csrc/ops_crf_lattice.hip states the formulas. */
+int cmpc_dense_crf_lattice(const float* sigm, const unsigned char* rgb, int B, int H, int W, float sxy_g, float compat_g, float sxy_b,
+                           float srgb, float compat_b, int iters, float* q_out, unsigned char* mask_out, void* stream);
 
 /* ---- Evaluation of a split (trainval_model.py:227-303, the `-m test` loop) at each sample's original size.  The resampler is
  *      skimage.transform.resize as cmpc-refseg_amd/hostutil.py restates it (mirror Gaussian when shrinking, then ndimage.zoom order 1,
