@@ -2154,6 +2154,7 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
     ECK(hipMalloc(&e->params, pbytes)); ECK(hipMalloc(&e->grads, pbytes)); ECK(hipMalloc(&e->adam_m, pbytes)); ECK(hipMalloc(&e->adam_v, pbytes));
     ECK(hipMemset(e->params, 0, pbytes)); ECK(hipMemset(e->grads, 0, pbytes)); ECK(hipMemset(e->adam_m, 0, pbytes)); ECK(hipMemset(e->adam_v, 0, pbytes));
     ECK(hipMalloc(&e->arena, e->arena_bytes)); ECK(hipMemset(e->arena, 0, e->arena_bytes));
+    tap(e, "packed_operands", e->arena, 3, {(int64_t)(e->arena_bytes / 4)});      // the packed operands' raw bytes (cmpc_operand_info)
     if (e->state_total > 0) {       // batch-norm moving statistics: mean 0, variance 1 (slim's initialisers)
         std::vector<float> init((size_t)e->state_total, 0.f);
         for (const auto& sp : e->state_specs)

@@ -415,7 +415,8 @@ __device__ __forceinline__ int seg_map(int x, int ns, const int (&src)[N], const
 __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ master, char* __restrict__ arena, const cmpc_pack_desc* __restrict__ descs,
                                                   const int* __restrict__ tile_prefix, int ndesc, int tile_begin,
                                                   const int* __restrict__ tile_desc) {
-    // tile = 64 (k) x 128 (n): float4 reads along n (every segment boundary is a multiple of 4); writes along n
+    // tile = 64 (k) x 128 (n): float4 reads along n where a lane's 4 columns map to 4 consecutive, 16-B aligned master elements, else
+    // element by element (a segment that ends or starts inside the 4 columns, or a row stride that is not a multiple of 4); writes along n
     // (natural, 8 / 16 B per lane) or along k through LDS (transposed: 8 k-values = one 16-B bf16 store per lane, a
     // full 128-B line per destination row).  LDS rows are 129 floats: both the scalar stores (element order rotated
     // per 8-lane group) and the column reads (lane -> 4 k-groups x 8 rows per half wave) are bank-conflict free.
@@ -433,20 +434,26 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ mas
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     char* dst = arena + d.dst_off;
     const int n = n0 + 4 * tx;
-    const int sc = (n < Np) ? seg_map(n, d.nns, d.ns_src, d.ns_len, d.ns_dst) : -1;
+    // source column of each of the lane's 4 columns (-1: padding); n < Np implies n + 3 < Np (Np is a multiple of 4)
+    int sc[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sc[e] = (n < Np) ? seg_map(n + e, d.nns, d.ns_src, d.ns_len, d.ns_dst) : -1;
+    const bool run4 = sc[0] >= 0 && sc[1] == sc[0] + 1 && sc[2] == sc[0] + 2 && sc[3] == sc[0] + 3;
+    const bool any = sc[0] >= 0 || sc[1] >= 0 || sc[2] >= 0 || sc[3] >= 0;
     const int rot = tx >> 3;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int kk = ty + 8 * i, k = k0 + kk;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (k < Kp && sc >= 0) {
+        if (k < Kp && any) {
             const int sr = seg_map(k, d.nks, d.ks_src, d.ks_len, d.ks_dst);
             if (sr >= 0) {
-                const float* src = master + d.src_off + (long)sr * d.ld_src + sc;
-                if ((d.ld_src & 3) == 0) v = *reinterpret_cast<const float4*>(src);
-                else {          // master rows that are not 16-B aligned (the 5-class parser of the video model, [500, 5]): scalar reads clipped to the row
-                    const int lim = d.ld_src - sc;
-                    v.x = src[0]; v.y = lim > 1 ? src[1] : 0.f; v.z = lim > 2 ? src[2] : 0.f; v.w = lim > 3 ? src[3] : 0.f;
+                const long row = d.src_off + (long)sr * d.ld_src;
+                if (run4 && ((row + sc[0]) & 3) == 0) v = *reinterpret_cast<const float4*>(master + row + sc[0]);
+                else {          // a segment end inside the 4 columns, or master rows that are not 16-B aligned (the video model's 5-class parser, [500, 5])
+                    const float* src = master + row;
+                    v.x = sc[0] >= 0 ? src[sc[0]] : 0.f; v.y = sc[1] >= 0 ? src[sc[1]] : 0.f;
+                    v.z = sc[2] >= 0 ? src[sc[2]] : 0.f; v.w = sc[3] >= 0 ? src[sc[3]] : 0.f;
                 }
             }
         }
@@ -598,6 +605,7 @@ extern "C" int cmpc_pack_weights_range(const float* master, void* arena, const c
                                        const int* tile_desc_dev, int ndesc, int tile_begin, int tile_end, void* stream) {
     if (ndesc <= 0 || tile_end <= tile_begin) return CMPC_OK;
     if (tile_begin < 0) { cmpc_set_error("pack_weights: bad tile range"); return CMPC_EINVAL; }
+    if (!master || !arena || !descs_dev || !tile_prefix_dev) { cmpc_set_error("pack_weights: null buffer"); return CMPC_EINVAL; }
     hipLaunchKernelGGL(pack_kernel, dim3(tile_end - tile_begin), dim3(256), 0, ST, master, (char*)arena, descs_dev, tile_prefix_dev, ndesc, tile_begin, tile_desc_dev);
     return cmpc_check_launch("pack_weights");
 }

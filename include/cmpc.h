@@ -316,7 +316,12 @@ typedef struct {
 } cmpc_pack_desc;
 /* tile_prefix_dev[i] = number of 64(k) x 128(n) tiles of descriptors 0..i-1 (exclusive prefix sum, ndesc+1
  * entries; tile count = ceil(K/64)*ceil(N/128) of each padded block); total_tiles = tile_prefix[ndesc].
- * Every K/N segment boundary, ld_src and src_off must be a multiple of 4 (float4 reads). */
+ * Every destination element is written: master[src_off + (ks_src + k - ks_dst) * ld_src + ns_src + n - ns_dst] inside a segment
+ * pair, 0 elsewhere (the padding), converted with round-to-nearest-even (f16: overflow to inf; NaN stays NaN).  Segments may start and
+ * end anywhere: columns are read as float4 where 4 of them map to consecutive, 16-B aligned master elements, element by element
+ * elsewhere.  Needs master and arena 16-B aligned, dst_off and ld_dst * element size multiples of 16, cols a multiple of 8
+ * (transpose) or 4, every segment inside [0, Kp) x [0, Np) of the block and inside the master rows it names, no two segments of one
+ * descriptor overlapping in the destination, and no two descriptors writing the same element. */
 int cmpc_pack_weights(const float* master, void* arena, const cmpc_pack_desc* descs_dev, const int* tile_prefix_dev,
                       int ndesc, int total_tiles, void* stream);
 /* the tiles [tile_begin, tile_end) only: lets the text encoder's operands (planned first) be published before the

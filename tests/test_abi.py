@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from tests import util as U
+from tests.packref import emulate_pack
 from tests.util import O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -80,19 +81,6 @@ def test_product_init_equals_oracle_init(pkg):
         assert torch.equal(pa[k], pb[k]), k
 
 
-def _emulate_pack(store, d, master):
-    """numpy restatement of pack_kernel for one descriptor."""
-    Kp, Np = (d.cols, d.rows) if d.transpose else (d.rows, d.cols)
-    blk = np.zeros((Kp, Np), dtype=np.float32)
-    for i in range(d.nks):
-        for j in range(d.nns):
-            ks, kl, kd = d.ks_src[i], d.ks_len[i], d.ks_dst[i]
-            ns, nl, nd = d.ns_src[j], d.ns_len[j], d.ns_dst[j]
-            rows = np.arange(ks, ks + kl)[:, None] * d.ld_src + np.arange(ns, ns + nl)[None, :]
-            blk[kd:kd + kl, nd:nd + nl] = master[d.src_off + rows]
-    return blk.T if d.transpose else blk
-
-
 def test_pack_tables_cover_operands_without_overlap(pkg):
     cfg = pkg.HeadCfg(batch_size=2, num_steps=6, vf_h=8, vf_w=8, H=64, W=64, vf_dim=256, c4_dim=128, c3_dim=64, vocab_size=50,
                       v_emb_dim=40, mlp_dim=24, rnn_size=40, glove_dim=12, parse_dim=20)
@@ -113,7 +101,7 @@ def test_pack_tables_cover_operands_without_overlap(pkg):
     # forward operand of the fusion layer: K segments skip the language rows (folded into a per-sample bias)
     master = np.arange(st.total, dtype=np.float32)
     d = [x for x in st._descs if x.dst_off == st.ops["fus_c5.t"].off][0]
-    blk = _emulate_pack(st, d, master)
+    blk = emulate_pack(d, master)
     C, M = cfg.v_emb_dim, cfg.mlp_dim
     off = st.poff("fusion_c5/DW")
     assert blk.shape == (cfg.Mp, 2 * cfg.Cp + 64)

@@ -542,7 +542,8 @@ def test_edge_cases_min_length_and_padding():
     assert abs(float(o["loss_all"].detach()) - scal["loss_all"]) <= 1e-5 * abs(scal["loss_all"])
 
 
-@pytest.mark.parametrize("B,T,h,w,C,M,seed", [(1, 1, 5, 5, 24, 16, 2), (5, 9, 7, 7, 72, 40, 15), (2, 24, 6, 9, 40, 24, 26), (3, 33, 4, 11, 136, 72, 36)])
+@pytest.mark.parametrize("B,T,h,w,C,M,seed", [(1, 1, 5, 5, 24, 16, 2), (5, 9, 7, 7, 72, 40, 15), (2, 24, 6, 9, 40, 24, 26), (3, 33, 4, 11, 136, 72, 36),
+                                              (2, 6, 8, 8, 30, 24, 3), (3, 7, 5, 6, 37, 16, 4)])
 def test_odd_shapes_match_oracle(B, T, h, w, C, M, seed):
     """Shapes nothing else exercises: batch 1 with a one-word sentence, an odd node count (7 x 7), a non-square map (6 x 9, 4 x 11), channel
     counts that are not multiples of 64 / 8, T at and beyond the streaming low-rank kernel's limit (24, 33): every tap, the losses and every

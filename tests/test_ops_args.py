@@ -257,3 +257,21 @@ def test_adam_limits(lib):
         p, g, m, v, segs = bufs
         _rejects(lib, "cmpc_adam_step", p, g, m, v, segs, 3, 1e-3, 0.9, 0.999, 1e-8, 1.0, None, None, msg="adam_step")
     assert lib.cmpc_adam_step(None, None, None, None, None, 0, 1e-3, 0.9, 0.999, 1e-8, 1.0, None, None) == 0     # nothing to do
+
+
+def test_pack_weights_limits(lib):
+    # args: master, arena, descs, tile_prefix, tile_desc, ndesc, tile_begin, tile_end, stream
+    _rejects(lib, "cmpc_pack_weights_range", P, P, P, P, None, 1, -1, 4, None, msg="tile range")
+    _rejects(lib, "cmpc_pack_weights_range", P, P, P, P, P, 3, -5, 1, None, msg="tile range")
+    for i in range(4):
+        bufs = [P, P, P, P]
+        bufs[i] = None
+        _rejects(lib, "cmpc_pack_weights_range", *bufs, None, 2, 0, 3, None, msg="pack_weights")
+        _rejects(lib, "cmpc_pack_weights", *bufs, 2, 3, None, msg="pack_weights")
+    # nothing to do: no descriptors, or an empty range (returns before any launch, whatever the pointers)
+    for nd in (0, -3):
+        assert lib.cmpc_pack_weights_range(None, None, None, None, None, nd, 0, 8, None) == 0
+        assert lib.cmpc_pack_weights(None, None, None, None, nd, 8, None) == 0
+    assert lib.cmpc_pack_weights_range(P, P, P, P, None, 2, 5, 5, None) == 0
+    assert lib.cmpc_pack_weights_range(P, P, P, P, None, 2, 6, 5, None) == 0
+    assert lib.cmpc_pack_weights(P, P, P, P, 2, 0, None) == 0
