@@ -4,13 +4,16 @@ gradient all-reduce + fused Adam) at 320x320, L=20, B=8 per GPU, synthetic data.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
   python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_out/run1   # + the last timed step's outputs as .npy
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full                          # + everything beyond the headline figure
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the project brief): metric/value/unit, ms_per_step,
-`roofline` for the dominant kernel family (the 16-bit MFMA gemm_nt, timed live with hipEvents on the launch
-stream inside the library: cmpc_kernel_timing) and `cpu_baseline` (the oracle -- a torch-CPU fp32 restatement of the reference graph,
-since TensorFlow cannot run here -- timed on this box's host cores on a bounded sample).
+Prints ONE JSON line on rank 0 (contract in the project brief): metric/value/unit, ms_per_step.  A plain run does only what that
+headline figure needs: set-up, W warm-up steps, K timed steps, --dump-outputs, the line.  --full adds, after the timed steps:
+`roofline` for the dominant kernel family (the 16-bit MFMA gemm_nt, timed live with hipEvents on the launch stream inside the
+library: cmpc_kernel_timing) with the per-kernel HBM / overall roofline beside it, the forward-only rate, the bf16-storage rate,
+BASELINE configs 4 and 5, and `cpu_baseline` (the oracle -- a torch-CPU fp32 restatement of the reference graph, since TensorFlow
+cannot run here -- timed on the host's cores on a bounded sample).  The --no-* switches leave single parts out of a --full run.
 """
 from __future__ import annotations
 
@@ -254,6 +257,9 @@ def main():
     ap.add_argument("--dtype", default="f16", choices=("f16", "bf16", "f32"),
                     help="storage of maps / visual GEMM operands. f16 and bf16 run the same MFMA pipelines at the same rate; f16 (default) is "
                          "the one that meets BASELINE's 1e-4 mean-IoU bar (bf16 storage: up to 1.6e-4), see tests/test_gpu_parity.py")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure what else the line can report: per-kernel timing and roofline, forward-only "
+                         "rate, bf16-storage rate, BASELINE configs 4 and 5, CPU baseline (off by default; the --no-* switches trim it)")
     ap.add_argument("--no-alt-dtype", action="store_true", help="skip the bf16-storage rate reported next to the f16 one")
     ap.add_argument("--cpu-images", type=int, default=8)
     ap.add_argument("--cpu-steps", type=int, default=2)
@@ -265,14 +271,15 @@ def main():
     ap.add_argument("--prefetch-gate", default="fwd", choices=("fwd", "bwd"), help="with --prefetch: the next batch's backbone starts behind this step's levels' forward / backward")
     ap.add_argument("--prefetch", action="store_true", help="hand train_step the next batch, whose backbone pass then runs behind this step's levels instead "
                     "of at the start of its own step (measured SLOWER: 11.2 vs 10.5 ms, DESIGN 7; off by default)")
-    ap.add_argument("--no-config4", action="store_true", help="skip the BASELINE config 4 rate reported inside the default line")
-    ap.add_argument("--no-config5", action="store_true", help="skip the BASELINE config 5 (video) rate reported inside the default line")
+    ap.add_argument("--no-config4", action="store_true", help="skip the BASELINE config 4 rate reported inside the --full line")
+    ap.add_argument("--no-config5", action="store_true", help="skip the BASELINE config 5 (video) rate reported inside the --full line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MB; rank 0). "
                          "bench_out/<tag> is ignored by git")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -343,7 +350,7 @@ def main():
     # same K steps re-run on ONE stream (same kernels, same shapes, same data), which is also how the committed rocprof
     # summary is collected.
     ktime = None
-    if not args.no_kernel_timing:
+    if full and not args.no_kernel_timing:
         model.set_lanes(1)
         model.train_step(words, im, target, seq_len)
         torch.cuda.synchronize()
@@ -355,12 +362,12 @@ def main():
         model.set_lanes(3 if int(os.environ.get("CMPC_STREAMS", "3")) > 1 else 1)
     # the second half of the roofline: every launch name timed on one stream, HBM-bound stages priced against their byte model
     trace = None
-    if not args.no_kernel_timing and world == 1 and not v5 and args.dtype != "f32":
+    if full and not args.no_kernel_timing and world == 1 and not v5 and args.dtype != "f32":
         trace = launch_trace(pkg, model, args.steps, (words, im, target, seq_len))
         model.set_lanes(3 if int(os.environ.get("CMPC_STREAMS", "3")) > 1 else 1)
     # forward-only rate (SURVEY 8d reports both): sess.run([pred, up, sigm]) on the same batch, same K
     dt_fwd = None
-    if not args.no_forward_only:
+    if full and not args.no_forward_only:
         for _ in range(2):
             model.forward(words, im, seq_len)
         barrier()
@@ -371,7 +378,7 @@ def main():
         dt_fwd = time.perf_counter() - t0
     # the same train step with bf16 storage (BASELINE config 2 names bf16): same kernels, same rate, misses the IoU bar
     alt = None
-    if world == 1 and args.dtype == "f16" and not args.no_alt_dtype and not v5:
+    if full and world == 1 and args.dtype == "f16" and not args.no_alt_dtype and not v5:
         del model
         torch.cuda.empty_cache()
         import warnings
@@ -391,12 +398,12 @@ def main():
         del m2
     # BASELINE config 4 (CMPCv5_BiLSTM + HSV branch, 512x512, L=25) on the same GPU: train-step and forward-only rate, reported inside the line
     cfg4 = None
-    if world == 1 and not v5 and not args.no_config4:
+    if full and world == 1 and not v5 and not args.no_config4:
         model = None
         torch.cuda.empty_cache()
         cfg4 = config4_rate(pkg, dev, args)
     cfg5 = None
-    if world == 1 and not v5 and not args.no_config5:
+    if full and world == 1 and not v5 and not args.no_config5:
         model = None
         torch.cuda.empty_cache()
         cfg5 = config5_rate(pkg, dev, args)
@@ -482,7 +489,7 @@ def main():
             out["config4"] = cfg4
         if cfg5 is not None:
             out["config5"] = cfg5
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline (oracle on host cores)")
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
