@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libcmpc_hip.so")
 
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 MODEL_CMPC, MODEL_V5_BILSTM, MODEL_VIDEO, MODEL_V5 = 0, 1, 2, 3
-ABI_VERSION = 3          # CMPC_ABI_VERSION of include/cmpc.h this binding was written against
+ABI_VERSION = 4          # CMPC_ABI_VERSION of include/cmpc.h this binding was written against
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
 
 
@@ -111,7 +111,7 @@ class EngineCfg(C.Structure):
 class Feeds(C.Structure):
     """cmpc_feeds"""
     _fields_ = [("words", C.c_void_p), ("seq_len", C.c_void_p), ("c3", C.c_void_p), ("c4", C.c_void_p), ("c5", C.c_void_p),
-                ("target_fine", C.c_void_p), ("feats_ready", C.c_void_p), ("c2", C.c_void_p), ("im", C.c_void_p), ("feats_ready_lv", C.c_void_p * 3), ("levels_done", C.c_void_p)]
+                ("target_fine", C.c_void_p), ("feats_ready", C.c_void_p), ("c2", C.c_void_p), ("im", C.c_void_p), ("levels_done", C.c_void_p)]
 
 
 class EvalDesc(C.Structure):
@@ -178,8 +178,6 @@ SIGNATURES = {
     "cmpc_lstm_cell_fwd": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "cmpc_lstm_cell_bwd": [_P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P],
     "cmpc_lstm_bwd_step": [_P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P],
-    "cmpc_lstm_seq_fwd": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "cmpc_lstm_seq_bwd": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "cmpc_parse_softmax_fwd": [_P, _I, _P, _P, _I, _I, _P],
     "cmpc_parse_softmax_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "cmpc_lang_pool_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

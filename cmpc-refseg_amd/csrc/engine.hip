@@ -246,7 +246,6 @@ struct ClstmStep { void *Yg, *c_pre, *c_new, *h_new, *dYg, *dc_prev, *dx, *dh; d
 struct LstmDir {
     std::string key, pk, pb;            // operand key ("lstm" / "lstm_fw" / "lstm_bw"), kernel / bias parameter names
     int* words_tb; float *emb, *xg, *gates, *h_all, *c_all, *outs, *douts, *dh, *dc, *dgt, *demb, *demb_parts;
-    int *sync_f, *sync_b;               // {barrier counter, abort flag} of the one-launch recurrence kernels (zeroed with the forward / backward regions)
 };
 // one slim conv2d + batch_norm + relu layer (CMPCv5_BiLSTM_model.py:190-251): the convolution's output, its statistics, the backward scratch
 struct BnLayer {
@@ -277,8 +276,7 @@ struct cmpc_engine_s {
     char* ws = nullptr; size_t ws_bytes = 0, zf_bytes = 0, zb_bytes = 0;
     void* zero_page = nullptr;
     // streams / events
-    hipStream_t lane[3] = {nullptr, nullptr, nullptr};       // the streams the three level / module chains run on (2 lanes: lane[2] = lane[0])
-    hipStream_t own_lane[3] = {nullptr, nullptr, nullptr};   // the streams this handle created
+    hipStream_t lane[3] = {nullptr, nullptr, nullptr};       // the streams (created by this handle) the three level / module chains run on
     std::vector<hipEvent_t> evpool; size_t evnext = 0;
     hipEvent_t ev_opt0 = nullptr, ev_opt1 = nullptr; bool opt_pending = false;
     std::vector<std::pair<char*, size_t>> guards;
@@ -339,8 +337,6 @@ struct cmpc_engine_s {
     void* tn_table[NBK][4] = {}; size_t tn_table_bytes = 0; std::vector<char> tn_shadow[NBK][4]; int tn_victim[NBK] = {};
     bool wgrad_overlap = true;          // issue the levels' / exchanges' dW beside the text encoder's backward chain
     bool lowrank = false;               // the graph's T-deep products through cmpc_lowrank_nn (16-bit storage, T <= 24, Cp = 4 * 2^j <= 1024)
-    bool mutan_epilogue = true;         // the Mutan heads' tanh as the epilogue of their GEMM (P is written once, as tanh; mutan_fwd only reads it)
-    bool lstm_seq = false;              // the text LSTM's T steps in ONE persistent launch per direction (B <= 8, Cp <= 1024; opt-in, see cmpc_create)
     cmpc_fold_ctx fold;                 // deferred bias / LayerNorm / peephole gradient folds (one launch per backward pass)
     std::vector<cmpc_fold_desc> fold_descs, fold_shadow[NBK]; cmpc_fold_desc* fold_table[NBK] = {}; int fold_shadow_n[NBK];
     std::vector<Tap> taps;
@@ -691,8 +687,6 @@ void plan_workspace(E* e, Bump& zf, Bump& zb, Bump& g) {
         D.dc = (float*)zb.take((size_t)B * Cp * F);
         D.dgt = (float*)g.take((size_t)T * B * 4 * Cp * F);
         D.demb = (float*)g.take((size_t)T * B * Gp * F); D.demb_parts = (float*)g.take((size_t)8 * T * B * Gp * F);
-        D.sync_f = (int*)zf.take(256); D.sync_b = (int*)zb.take(256);
-        tap(e, fmt("lstm_sync_%d", d), D.sync_f, 3, {2}); tap(e, fmt("lstm_sync_bwd_%d", d), D.sync_b, 3, {2});
     }
     if (e->bilstm) {
         e->outs_bw = (float*)g.take((size_t)B * T * Cp * F); e->douts_bw = (float*)g.take((size_t)B * T * Cp * F);
@@ -1058,8 +1052,6 @@ int lstm_dir_fwd(E* e, hipStream_t st, LstmDir& D, const int32_t* seq_len) {
     GemmOpt o; o.bias = (const float*)opp(e, D.key + ".b");
     CK(gemm_nt(st, DT_F32, {{D.emb, Gp, opp(e, D.key + ".t"), ldk, Gp}}, D.xg, 4 * Cp, T * B, 4 * Cp, o));
     const void* wh = opp(e, D.key + ".t", 0, Gp);
-    if (e->lstm_seq)      // all T steps in one persistent launch (W_h in registers, a grid barrier per step)
-        return cmpc_lstm_seq_fwd(D.xg, (const float*)wh, ldk, seq_len, D.gates, D.h_all, D.c_all, D.outs, D.sync_f, B, T, Cp, R, st);
     for (int t = 0; t < T; ++t) {
         float* gt = D.gates + (size_t)t * B * 4 * Cp;
         float *hp = D.h_all + (size_t)t * B * Cp, *cp = D.c_all + (size_t)t * B * Cp;
@@ -1075,9 +1067,7 @@ int lstm_dir_bwd(E* e, hipStream_t st, LstmDir& D, const int32_t* seq_len) {
     auto gat = [&](int t) { return D.gates + (size_t)t * B * 4 * Cp; };
     auto call = [&](int t) { return D.c_all + (size_t)t * B * Cp; };
     auto dgt = [&](int t) { return D.dgt + (size_t)t * B * 4 * Cp; };
-    if (e->lstm_seq) {
-        CK(cmpc_lstm_seq_bwd((const float*)opp(e, D.key + ".n", Gp, 0), 4 * Cp, D.gates, D.c_all, seq_len, D.douts, D.dgt, D.sync_b, B, T, Cp, R, st));
-    } else if (B <= 8) {
+    if (B <= 8) {
         // one launch per step: dh += dg[t] . W_h^T fused with the cell backward of step t-1
         CK(cmpc_lstm_cell_bwd(gat(T - 1), call(T - 1), call(T), seq_len, T - 1, D.douts + (size_t)(T - 1) * Cp, T * Cp, D.dh, D.dc, dgt(T - 1), B, Cp, R, st));
         const float* wn = (const float*)opp(e, D.key + ".n", Gp, 0);
@@ -1254,9 +1244,9 @@ int level_fwd(E* e, hipStream_t st, int li, const float* target) {
     }
     // -- mutan_fusion (:295-328)
     { const int ldk = Cp + 64; const std::string k = fmt("mutan_%s.t", lv);
-      GemmOpt p; p.bias = (const float*)opp(e, fmt("mutan_%s.b", lv)); if (e->mutan_epilogue) p.act = ACT_TANH;
+      GemmOpt p; p.bias = (const float*)opp(e, fmt("mutan_%s.b", lv)); p.act = ACT_TANH;      // P is written once, as tanh; mutan_fwd only reads it
       CK(gemm_nt(st, dt, {{L.X0, Cp, opp(e, k), ldk, Cp}, {e->spatial, 64, opp(e, k, 0, Cp), ldk, 64}}, L.P, 5 * Cp, R, 5 * Cp, p));
-      CK(cmpc_mutan_fwd(dt, L.P, L.g, L.X1, L.mut_rstd, B, N, Cp, C, e->mutan_epilogue ? 1 : 0, st)); }
+      CK(cmpc_mutan_fwd(dt, L.P, L.g, L.X1, L.mut_rstd, B, N, Cp, C, 1, st)); }
     // -- build_spa_graph + graph_conv (:359-410); adjacency never formed, trans2 folded into the word side
     { const float scale = 1.0f / sqrtf((float)C);
       GemmOpt c; c.batch = B; c.sC = (int64_t)N * Tp; c.c_f32 = 1; c.alpha = scale; c.sbias = L.k0s; c.ld_sbias = Tp; c.rows_per_sample = N;
@@ -1453,9 +1443,9 @@ int level_fwd_video(E* e, hipStream_t st, int li, const float* target) {
       CK(gemm_nt(st, dt, {{L.feat, L.cin, opp(e, fmt("lat_%s.t", lv)), L.cin, L.cin}}, L.X0, Cp, RF, Cp, o));
       CK(cmpc_l2norm_rows_fwd(dt, L.X0, L.X0, L.lat_rstd, nullptr, RF, Cp, C, st)); }
     { const int ldk = Cp + 64; const std::string k = fmt("mutan_%s.t", lv);
-      GemmOpt p; p.bias = (const float*)opp(e, fmt("mutan_%s.b", lv)); if (e->mutan_epilogue) p.act = ACT_TANH;
+      GemmOpt p; p.bias = (const float*)opp(e, fmt("mutan_%s.b", lv)); p.act = ACT_TANH;
       CK(gemm_nt(st, dt, {{L.X0, Cp, opp(e, k), ldk, Cp}, {e->spatial, 64, opp(e, k, 0, Cp), ldk, 64}}, L.P, 5 * Cp, RF, 5 * Cp, p));
-      CK(cmpc_mutan_fwd(dt, L.P, L.g, L.X1, L.mut_rstd, Fr, N, Cp, C, e->mutan_epilogue ? 1 : 0, st)); }
+      CK(cmpc_mutan_fwd(dt, L.P, L.g, L.X1, L.mut_rstd, Fr, N, Cp, C, 1, st)); }
     // -- temporal graph (vid:458-503): per-frame attention pooling with the action vector, 5 x 5 adjacency, graph_conv, l2norm
     CK(cmpc_rowdot1(dt, L.X1, L.kqv, 0, L.tlog, Fr, N, Cp, C, scale, st));
     CK(cmpc_softmax_n_fwd(L.tlog, L.tatt, Fr, N, st));
@@ -2048,7 +2038,7 @@ extern "C" int cmpc_destroy(cmpc_handle e) {
     for (void* p : {(void*)e->params, (void*)e->grads, (void*)e->adam_m, (void*)e->adam_v, (void*)e->arena, (void*)e->descs_dev,
                     (void*)e->tile_prefix_dev, (void*)e->tile_desc_dev, (void*)e->segs_dev, (void*)e->ws, (void*)e->bn_state})
         if (p) (void)hipFree(p);
-    for (hipStream_t s : e->own_lane) if (s) { cmpc_ws_release(s); (void)hipStreamDestroy(s); }
+    for (hipStream_t s : e->lane) if (s) { cmpc_ws_release(s); (void)hipStreamDestroy(s); }
     for (hipEvent_t ev : e->evpool) (void)hipEventDestroy(ev);
     if (e->ev_opt0) (void)hipEventDestroy(e->ev_opt0);
     if (e->ev_opt1) (void)hipEventDestroy(e->ev_opt1);
@@ -2075,7 +2065,7 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
     // every model runs the ConvLSTM and the exchange modules on [*, pad64(mlp_dim)] maps: two column blocks of 512 at most, and peephole rows
     // of mlp_dim floats read as float4
     if (pad64(c->mlp_dim) > 1024 || c->mlp_dim % 4) { cmpc_set_error("create: mlp_dim a multiple of 4 with pad64(mlp_dim) <= 1024 (ConvLSTM, exchange modules)"); return CMPC_EINVAL; }
-    if (c->n_lanes < 1 || c->n_lanes > 3) { cmpc_set_error("create: n_lanes must be 1, 2 or 3"); return CMPC_EINVAL; }
+    if (c->n_lanes != 1 && c->n_lanes != 3) { cmpc_set_error("create: n_lanes must be 1 or 3"); return CMPC_EINVAL; }
     if (c->model != CMPC_MODEL_CMPC && c->model != CMPC_MODEL_V5_BILSTM && c->model != CMPC_MODEL_VIDEO && c->model != CMPC_MODEL_V5) {
         cmpc_set_error("create: model must be CMPC_MODEL_CMPC (0), CMPC_MODEL_V5_BILSTM (1), CMPC_MODEL_VIDEO (2) or CMPC_MODEL_V5 (3)"); return CMPC_EINVAL;
     }
@@ -2211,8 +2201,7 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
         std::vector<float> on((size_t)e->B * e->N, 1.0f / (float)e->N);       // tf.reduce_mean over the map (v5:242)
         ECK(hipMemcpy(e->ones_n, on.data(), on.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    for (int i = 0; i < 3; ++i) { ECK(hipStreamCreateWithFlags(&e->own_lane[i], hipStreamNonBlocking)); e->lane[i] = e->own_lane[i]; }
-    if (c->n_lanes == 2) e->lane[2] = e->lane[0];
+    for (auto& s : e->lane) ECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     e->evpool.resize(256);
     for (auto& ev : e->evpool) { ev = nullptr; ECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); }
     ECK(hipEventCreateWithFlags(&e->ev_opt0, hipEventDisableTiming));
@@ -2220,12 +2209,6 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
     ECK(hipEventCreateWithFlags(&e->ev_grid_read, hipEventDisableTiming));
     for (auto& d : e->deferred) d.reserve(128);
     if (const char* v = getenv("CMPC_WGRAD_OVERLAP")) e->wgrad_overlap = atoi(v) != 0;       // read once, at create
-    if (const char* v = getenv("CMPC_MUTAN_EPILOGUE")) e->mutan_epilogue = atoi(v) != 0;
-    // Opt-in (CMPC_LSTM_SEQ=1): measured SLOWER inside the multi-stream step (13.26 vs 10.71 ms per B=8 train step): its 256 spinning
-    // workgroups cannot co-reside with the MFMA kernels of the other streams (2 waves x 256 VGPRs per SIMD fill the register file), so every
-    // grid barrier waits for whole GEMM / persistent dW workgroups to retire.  It pays only where the recurrence has the GPU to itself.
-    e->lstm_seq = false;
-    if (const char* v = getenv("CMPC_LSTM_SEQ")) e->lstm_seq = atoi(v) != 0 && e->B <= 8 && e->Cp <= 1024;
     e->fold_descs.resize(e->fold.table_cap);
     for (int a = 0; a < E::NBK; ++a) { e->fold_shadow[a].resize(e->fold.table_cap); e->fold_shadow_n[a] = -1; }
     e->fold.descs = e->fold_descs.data(); e->fold.shadow = e->fold_shadow[E::NBK - 1].data();
@@ -2424,9 +2407,8 @@ extern "C" int cmpc_phase_marks_read(cmpc_handle e, int index, const char** name
     return CMPC_OK;
 }
 extern "C" int cmpc_set_lanes(cmpc_handle e, int n_lanes) {
-    if (!e || n_lanes < 1 || n_lanes > 3) { cmpc_set_error("set_lanes: n_lanes must be 1, 2 or 3"); return CMPC_EINVAL; }
+    if (!e || (n_lanes != 1 && n_lanes != 3)) { cmpc_set_error("set_lanes: n_lanes must be 1 or 3"); return CMPC_EINVAL; }
     e->cfg.n_lanes = n_lanes;
-    e->lane[2] = n_lanes == 2 ? e->own_lane[0] : e->own_lane[2];
     return CMPC_OK;
 }
 extern "C" int cmpc_kernel_timing(cmpc_handle e, int enable) {
@@ -2531,10 +2513,8 @@ extern "C" int cmpc_forward(cmpc_handle e, const cmpc_feeds* f, const cmpc_fetch
         e->bwd_zeroed = true;
     }
     for (int i = 0; i < NL; ++i) { CK(e->vid ? level_lang_fwd_video(e, st[i], i) : level_lang_fwd(e, st[i], i)); CK(exchange_lang_fwd(e, st[i], i)); CK(exchange_lang_fwd(e, st[i], NX + i)); }
-    for (int i = 0; i < 3; ++i) {           // every lane waits for its own tap when the caller says when each is complete, else for all of them
-        void* ev = f->feats_ready_lv[i] ? f->feats_ready_lv[i] : f->feats_ready;
-        if (ev) HCK(hipStreamWaitEvent(st[i], (hipEvent_t)ev, 0));       // one lane: st[0..2] are the caller's stream, which then waits for all three
-    }
+    if (f->feats_ready)                     // one lane: st[0..2] are the caller's stream
+        for (hipStream_t s : st) HCK(hipStreamWaitEvent(s, (hipEvent_t)f->feats_ready, 0));
     CK(mark(e, "fwd:feats_ready", st[0]));
     if (e->v5) {
         // hsv:120-126 (the image feed only) before the levels that read it; the decoder's low-level branch (backbone only) on the idle third lane

@@ -431,21 +431,20 @@ class VideoEvaluator:
                     ready.record(bb)
                 proc.record_stream(main)
                 feats, done = m.features_async(feed[:len(fr)], ready=ready)
-                clip = (feats, done, m._tap_events, ids, seq, proc, gt, self.n)
+                clip = (feats, done, ids, seq, proc, gt, self.n)
                 self._head(self.pending)
                 self.pending = clip
             else:
                 feed, proc, ids, seq = self._stage(we, sl, fr, im)
                 feats, done = m.features_async(feed[:len(fr)])
-                self._head((feats, done, m._tap_events, ids, seq, proc, gt, self.n))
+                self._head((feats, done, ids, seq, proc, gt, self.n))
         self.n += 1
 
     def _head(self, clip):
         if clip is None:
             return
-        feats, done, tap_events, ids, seq, proc, gt, i = clip
+        feats, done, ids, seq, proc, gt, i = clip
         m = self.model
-        m._tap_events = tap_events          # CMPC_BB_STAGED: the per-level events of THIS clip's backbone pass
         out = m._video_fetch(feats, done, ids, seq)
         self._grow(i + 1)
         mask_iu(out["up"].float(), [gt], self.score_thresh, out=self.iu[i: i + 1])

@@ -28,8 +28,9 @@ extern "C" {
 const char* cmpc_last_error(void);
 /* Bumped whenever an exported signature or structure changes incompatibly; a binding must refuse a library whose version differs
  * (cmpc-refseg_amd/_lib.py does).  2: stat blocks (double[n][CMPC_STAT_PARTS][2]) replace double[B][2] sums, cmpc_mutan_fwd gained
- * pre_tanh, cmpc_adam_step gained `nonfinite`, cmpc_cfg gained `model`.  3: cmpc_feeds gained `levels_done`, n_lanes may be 2 */
-#define CMPC_ABI_VERSION 3
+ * pre_tanh, cmpc_adam_step gained `nonfinite`, cmpc_cfg gained `model`.  3: cmpc_feeds gained `levels_done`, n_lanes may be 2.
+ * 4: cmpc_lstm_seq_* removed, cmpc_feeds lost feats_ready_lv, n_lanes is 1 or 3 */
+#define CMPC_ABI_VERSION 4
 int cmpc_abi_version(void);
 
 /* ---- GEMMs: every _conv 1x1 (CMPC_model.py:412-417), tf.matmul (:173,187,226,235,362,384,400)
@@ -242,15 +243,6 @@ int cmpc_lstm_cell_bwd(const float* gates_act, const float* c_prev, const float*
 int cmpc_lstm_bwd_step(const float* dgates_t, const float* Wn, int ldw, const float* gates_act_tm1, const float* c_prev, const float* c_out,
                        const int* seq_len, int tm1, const float* dout_tm1, int ld_dout, float* dh, float* dc, float* dgates_tm1,
                        int B, int ld, int R, void* stream);
-/* The whole recurrence of one direction in ONE launch (persistent workgroups, W_h in registers, a grid barrier per step; B <= 8, ld <= 1024,
- * otherwise CMPC_EINVAL: use the per-step entry points).  xg [T, B, 4 ld]: x-side pre-activations incl. bias; Wh [4 ld rows][ldw]: gate rows of W_h,
- * k contiguous; gates [T, B, 4 ld] receives the activated gates; h_all / c_all [(T+1), B, ld], slice 0 = initial state; outs [B, T, ld];
- * sync: 8 bytes of ZEROED device memory per launch (barrier counter + abort flag: non-zero afterwards = the launch was aborted by its watchdog).
- * cmpc_lstm_seq_bwd: dgates [T, B, 4 ld] from douts [B, T, ld]; Wn [ld rows][4 ld] = rows of W_h^T */
-int cmpc_lstm_seq_fwd(const float* xg, const float* Wh, int ldw, const int* seq_len, float* gates, float* h_all, float* c_all, float* outs,
-                      void* sync, int B, int T, int ld, int R, void* stream);
-int cmpc_lstm_seq_bwd(const float* Wn, int ldw, const float* gates, const float* c_all, const int* seq_len, const float* douts, float* dgates,
-                      void* sync, int B, int T, int ld, int R, void* stream);
 /* softmax over the 4 parser classes times seq_mask (:352-353) */
 /* ncls classes per word (4: CMPC_model.py:351; 5: CMPC_video_mm_tgraph_allvec.py:406); parse rows are ncls wide */
 int cmpc_parse_softmax_fwd(const float* logits, int ld, const float* mask, float* parse, int n, int ncls, void* stream);
@@ -366,7 +358,7 @@ typedef struct {
     float loss_scale;                   /* every gradient cmpc_backward writes is multiplied by it and cmpc_optimizer_step divides
                                            it out again; 0 = default (1; for f16 storage the power of two that keeps the largest upstream
                                            gradient, loss_w[0] * (H/vf_h) * (W/vf_w) / batch_size, at <= 16) */
-    int n_lanes;                        /* 3: pyramid levels / exchange modules on three lane streams; 1: one stream */
+    int n_lanes;                        /* 3: pyramid levels / exchange modules on three lane streams; 1: one stream; no other value */
     int device;                         /* HIP device ordinal; -1 = planning only (manifest, operand plan, workspace size:
                                            no GPU is touched; every compute entry point then returns CMPC_EINVAL) */
     /* which graph: get_model.get_segmentation_model(name) (get_model.py:15-17) */
@@ -442,9 +434,6 @@ typedef struct {
                                    is enqueued first and only the pyramid levels wait for it; NULL = ordered on `stream` */
     const void* c2;             /* models V5_BILSTM / V5: res2b_relu [B, c2_h, c2_w, c2_dim] NHWC, cfg.dtype (v5:88); c3 is unused there (may be NULL) */
     const float* im;            /* models V5_BILSTM / V5 with hsv: the image feed itself [B, H, W, 3] f32, BGR minus mean (v5:80; hsv:120-126) */
-    void* feats_ready_lv[3];    /* optional, per pyramid level (c5, c4, c3 -- for V5_BILSTM slot 2 is the res2b tap): hipEvent_t recorded once THAT tap is
-                                   complete; a level's lane then waits for its own tap only (c3 leaves the backbone after res3, c4 after res4), NULL
-                                   entries fall back to feats_ready */
     void* levels_done;          /* optional hipEvent_t that cmpc_forward RECORDS once the pyramid levels' forward is complete: from there to the
                                    levels' backward the step is a serial chain of small launches (exchange modules, ConvLSTM, scores), the
                                    window a caller uses for independent heavy work -- the frozen backbone of the NEXT batch */

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of the step schedule on one box: prefetch of the next batch's backbone (behind the levels' forward) x lanes, at the runtime's
+# A/B of the step schedule on one box: prefetch of the next batch's backbone (behind the levels' forward) on and off, at the runtime's
 # default hardware-queue count (raising GPU_MAX_HW_QUEUES is not done on shared machines).
 cd $GRAFT_REPO_ROOT
 run() { # label, env..., -- bench args
@@ -10,6 +10,4 @@ run() { # label, env..., -- bench args
 for rep in 1 2; do
 EXTRA="" run "base  lanes3 q4" CMPC_STREAMS=3
 EXTRA="--prefetch"            run "pref  lanes3 q4" CMPC_STREAMS=3
-EXTRA="--prefetch"            run "pref  lanes2 q4" CMPC_STREAMS=2
-EXTRA="" run "base  lanes2 q4" CMPC_STREAMS=2
 done

@@ -294,12 +294,11 @@ def test_head_16bit_within_tolerance(case, dtype, tap_tol, loss_tol, grad_tol):
     assert max(errs.values()) < grad_tol, errs
 
 
-@pytest.mark.parametrize("switch", ["CMPC_LOWRANK", "CMPC_MUTAN_EPILOGUE", "CMPC_WGRAD_OVERLAP", "CMPC_LSTM_SEQ"])
+@pytest.mark.parametrize("switch", ["CMPC_LOWRANK", "CMPC_WGRAD_OVERLAP"])
 def test_alternative_paths_agree(case, switch, monkeypatch):
     """The A/B switches read by cmpc_create select paths that are also the fall-backs of other configurations (the graph's T-deep
-    products through gemm_nt when T > 24 / C > 1024, the Mutan tanh inside mutan_fwd, the dW launches after the text encoder, the per-step
-    LSTM launches when B > 8): on the
-    same f16 inputs they agree with the default path to rounding (every tap, the loss, a gradient per stage)."""
+    products through gemm_nt when T > 24 / C > 1024, the dW launches after the text encoder): on the same f16 inputs they agree with
+    the default path to rounding (every tap, the loss, a gradient per stage)."""
     def run():
         m = _model(case, "f16")
         o = m.loss_and_grads([f.to(m.device) for f in case["feats"]], case["words"], case["tgt"], case["sl"])
@@ -307,12 +306,7 @@ def test_alternative_paths_agree(case, switch, monkeypatch):
         taps = {k: v.float().cpu().clone() for k, v in U.product_taps_as_oracle(o, case["cfg"]).items()}
         return taps, float(o["loss_all"]), {k: v.cpu().clone() for k, v in m.store.grad_dict().items()}
     ta, la, ga = run()
-    monkeypatch.setenv(switch, "1" if switch == "CMPC_LSTM_SEQ" else "0")         # the one-launch recurrence is opt-in, the others opt-out
-    if switch == "CMPC_LSTM_SEQ":       # it runs, and its watchdog stays quiet
-        m = _model(case, "f16")
-        m.loss_and_grads([f.to(m.device) for f in case["feats"]], case["words"], case["tgt"], case["sl"])
-        torch.cuda.synchronize()
-        assert int(m.eng.tap("lstm_sync_0")[1]) == 0 and int(m.eng.tap("lstm_sync_bwd_0")[1]) == 0 and int(m.eng.tap("lstm_sync_0")[0]) > 0
+    monkeypatch.setenv(switch, "0")
     tb, lb, gb = run()
     for k in ta:
         assert U.rel_err(tb[k], ta[k]) < 3e-3, (switch, k)
@@ -378,11 +372,11 @@ def test_loss_curve_60_steps_follows_oracle():
         assert m.grad_nonfinite() == 0
 
 
-def test_one_lane_equals_three_lanes(case):
+def test_one_and_three_lanes_are_bit_identical(case):
     """The lane streams only reorder independent stages, and no sum depends on scheduling: the handle with n_lanes = 1 (everything
     on the caller's stream) and with 3 lanes gives bit-identical scalars and parameters after 3 steps with changing feeds."""
     ms = []
-    for lanes in (3, 1, 2):
+    for lanes in (3, 1):
         P = U.pkg()
         m = P.LSTM_model(head_params=case["hp"], backbone_params=case["bp"], n_lanes=lanes, **U.model_kwargs(case["cfg"], "f32"))
         scal = None
