@@ -169,6 +169,9 @@ SIGNATURES = {
     "cmpc_convlstm_c": [_I, _P, _P, C.POINTER(ConvLstmLn), _P, _P, _P, _I, _I, _I, _I, _P],
     "cmpc_convlstm_bwd": [_I, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ConvLstmLn), _P, _P, _P,
                           _P, _P, _P, C.POINTER(ConvLstmDln), _P, _P, _I, _I, _I, _I, _P],
+    "cmpc_convlstm_bwd_gates": [_I, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ConvLstmLn), _P, _P, _P,
+                                C.POINTER(ConvLstmDln), _P, _P, _I, _I, _I, _I, _P],
+    "cmpc_convlstm_peephole_grad": [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "cmpc_score_conv_fwd": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "cmpc_score_conv_bwd": [_I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "cmpc_upsample_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -246,6 +249,10 @@ COUNTS = {"cmpc_param_count": [_P], "cmpc_tap_count": [_P], "cmpc_grad_bucket_co
 _lib = None
 
 
+# op-level entry points younger than the oldest build still used as the `prev` side of an A/B run; nothing in the package calls them
+_AB_OPTIONAL = ("cmpc_convlstm_bwd_gates", "cmpc_convlstm_peephole_grad")
+
+
 def load():
     """Load the shared library (once) and attach prototypes; raises if it has not been built."""
     global _lib
@@ -269,6 +276,8 @@ def load():
         lib.cmpc_crc32c.restype = C.c_uint32
         lib.cmpc_crc32c.argtypes = [C.c_uint32, C.c_void_p, C.c_size_t]
     for name, argtypes in SIGNATURES.items():
+        if name in _AB_OPTIONAL and "CMPC_LIB_PATH" in os.environ and not hasattr(lib, name):
+            continue                     # an older build named for an A/B run (scripts/ab_bench.sh); the in-tree library stays strict
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = C.c_int
         fn.argtypes = argtypes

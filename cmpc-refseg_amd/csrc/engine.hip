@@ -1061,8 +1061,10 @@ int lstm_dir_fwd(E* e, hipStream_t st, LstmDir& D, const int32_t* seq_len) {
     }
     return CMPC_OK;
 }
-// in: D.douts (gradient of the direction's outputs [B, T, Cp]); out: kernel / bias gradients (deferred), D.demb (not yet scattered)
-int lstm_dir_bwd(E* e, hipStream_t st, LstmDir& D, const int32_t* seq_len) {
+// in: D.douts (gradient of the direction's outputs [B, T, Cp]); out: kernel / bias gradients (deferred), D.demb (not yet scattered).
+// Two parts: lstm_dir_bwd_rec is the recurrence, after which the kernel-gradient products have their operands (D.dgt, D.emb, D.h_all) and
+// are registered; lstm_dir_bwd_rest the bias column sums and the embedding gradient, which the products do not read.
+int lstm_dir_bwd_rec(E* e, hipStream_t st, LstmDir& D, const int32_t* seq_len) {
     const int B = e->B, T = e->T, R = e->RNN, G = e->G, Cp = e->Cp, Gp = e->Gp;
     auto gat = [&](int t) { return D.gates + (size_t)t * B * 4 * Cp; };
     auto call = [&](int t) { return D.c_all + (size_t)t * B * Cp; };
@@ -1086,7 +1088,10 @@ int lstm_dir_bwd(E* e, hipStream_t st, LstmDir& D, const int32_t* seq_len) {
     for (int g = 0; g < 4; ++g) { o0.push_back({0, (int64_t)g * Cp, (int64_t)g * R}); o1.push_back({0, (int64_t)g * Cp, (int64_t)G * 4 * R + (int64_t)g * R}); }
     TnOpt d; d.defer = true;
     CK(gemm_tn(e, st, DT_F32, D.emb, Gp, Gp, D.dgt, 4 * Cp, Cp, gk, 4 * R, T * B, G, R, o0, d));
-    CK(gemm_tn(e, st, DT_F32, D.h_all, Cp, Cp, D.dgt, 4 * Cp, Cp, gk, 4 * R, T * B, R, R, o1, d));
+    return gemm_tn(e, st, DT_F32, D.h_all, Cp, Cp, D.dgt, 4 * Cp, Cp, gk, 4 * R, T * B, R, R, o1, d);
+}
+int lstm_dir_bwd_rest(E* e, hipStream_t st, LstmDir& D) {
+    const int B = e->B, T = e->T, R = e->RNN, G = e->G, Cp = e->Cp, Gp = e->Gp;
     float* gb = gptr(e, D.pb);
     for (int g = 0; g < 4; ++g) CK(colsum(st, DT_F32, D.dgt + (size_t)g * Cp, T * B, 4 * Cp, Cp, R, gb + (size_t)g * R));
     {   // demb = dg . W_x^T: a small output ([T*B, G]) over a long reduction (4 Cp) -> split-K as a batched product + one sum
@@ -1132,12 +1137,33 @@ int text_fwd(E* e, hipStream_t st, const int32_t* words, const int32_t* seq_len)
     CK(gemm_nt(st, DT_F32, {{F.outs, Cp, opp(e, "wfeat.t"), 2 * Cp, Cp}, {e->outs_bw, Cp, opp(e, "wfeat.t", 0, Cp), 2 * Cp, Cp}}, e->wft, Cp, B * T, Cp, o));
     return cmpc_l2norm_rows_fwd(DT_F32, e->wft, e->wf, e->wf_rstd, nullptr, B * T, Cp, R, st);          // v5:185
 }
-int text_bwd(E* e, hipStream_t st, const int32_t* seq_len) {
+// The text bucket's grouped weight-gradient launch, issued as soon as the recurrences are enqueued: on `wst` (the stream that carried the
+// levels' buckets; ordered here behind `st` and, for the second direction, `sb`), beside the column sums, the embedding-gradient product
+// and the scatter that follow on `st`.  Its products write kernel / DW ranges of the gradient buffer, what follows on `st` writes bias
+// rows (through the deferred folds) and `Variable`.  *dw_done: what the bucket's second half (flush_bucket_folds) must wait for.
+int flush_bucket_dw(E* e, hipStream_t st, int b);
+int text_issue_dw(E* e, hipStream_t st, hipStream_t sb, hipStream_t wst, hipEvent_t* dw_done) {
+    if (wst != st) {
+        hipEvent_t ev = next_event(e);
+        HCK(hipEventRecord(ev, st));
+        HCK(hipStreamWaitEvent(wst, ev, 0));
+        if (sb != st && sb != wst) { hipEvent_t evb = next_event(e); HCK(hipEventRecord(evb, sb)); HCK(hipStreamWaitEvent(wst, evb, 0)); }
+    } else if (sb != st) {
+        hipEvent_t evb = next_event(e); HCK(hipEventRecord(evb, sb)); HCK(hipStreamWaitEvent(wst, evb, 0));
+    }
+    CK(flush_bucket_dw(e, wst, E::NBK - 1));
+    CK(mark(e, "bwd:text_dW_issued", wst));
+    if (wst != st) { *dw_done = next_event(e); HCK(hipEventRecord(*dw_done, wst)); }
+    return CMPC_OK;
+}
+int text_bwd(E* e, hipStream_t st, const int32_t* seq_len, hipStream_t wst, hipEvent_t* dw_done) {
     const int B = e->B, T = e->T, R = e->RNN, G = e->G, Cp = e->Cp, Gp = e->Gp;
     LstmDir& F = e->ldir[0];
     if (!e->bilstm) {
         CK(cmpc_l2norm_rows_bwd(DT_F32, e->dwf, e->wf, e->wf_rstd, F.douts, B * T, Cp, R, 0, st));
-        CK(lstm_dir_bwd(e, st, F, seq_len));
+        CK(lstm_dir_bwd_rec(e, st, F, seq_len));
+        CK(text_issue_dw(e, st, st, wst, dw_done));
+        CK(lstm_dir_bwd_rest(e, st, F));
         return cmpc_embed_scatter(F.demb, Gp, F.words_tb, gptr(e, "Variable"), T * B, G, e->V, st);
     }
     LstmDir& W = e->ldir[1];
@@ -1161,9 +1187,12 @@ int text_bwd(E* e, hipStream_t st, const int32_t* seq_len) {
         HCK(hipStreamWaitEvent(sb, ev, 0));
     }
     CK(cmpc_reverse_sequence(e->douts_bw, W.douts, seq_len, B, T, Cp, sb));
-    CK(lstm_dir_bwd(e, sb, W, seq_len));
+    CK(lstm_dir_bwd_rec(e, sb, W, seq_len));
+    CK(lstm_dir_bwd_rec(e, st, F, seq_len));
+    CK(text_issue_dw(e, st, sb, wst, dw_done));
+    CK(lstm_dir_bwd_rest(e, sb, W));
     if (sb != st) { back = next_event(e); HCK(hipEventRecord(back, sb)); }
-    CK(lstm_dir_bwd(e, st, F, seq_len));
+    CK(lstm_dir_bwd_rest(e, st, F));
     if (back) HCK(hipStreamWaitEvent(st, back, 0));
     // both directions add into the one embedding table: two scatters in a fixed order on one stream (one writer per row each)
     CK(cmpc_embed_scatter(F.demb, Gp, F.words_tb, gptr(e, "Variable"), T * B, G, e->V, st));
@@ -1282,7 +1311,16 @@ int level_fwd(E* e, hipStream_t st, int li, const float* target) {
 }
 
 // dfus (the level's fusion-output gradient from the exchange modules) must already hold the sum of its consumers
-int level_bwd(E* e, hipStream_t st, int li, const float* target) {
+// ls: the stream of the launches that feed only the text encoder's backward (dvl, dk0s -> dWd -> dwf, the lang_trans column sums), each
+// group behind an event on st; ls == st keeps them in line
+int level_bwd(E* e, hipStream_t st, int li, const float* target, hipStream_t ls) {
+    auto hand = [&]() -> int {
+        if (ls == st) return CMPC_OK;
+        hipEvent_t ev = next_event(e);
+        HCK(hipEventRecord(ev, st));
+        HCK(hipStreamWaitEvent(ls, ev, 0));
+        return CMPC_OK;
+    };
     LevelBuf& L = e->lv[li]; const char* lv = lvn(e, li);
     const int B = e->B, N = e->N, T = e->T, R = e->R, C = e->C, Cp = e->Cp, Tp = e->Tp, M = e->M, Mp = e->Mp, dt = e->dt, Rr = e->RNN;
     const int es = e->esz;
@@ -1303,7 +1341,8 @@ int level_bwd(E* e, hipStream_t st, int li, const float* target) {
       CK(gemm_nt(st, dt, {{L.dpre, Mp, opp(e, k), Mp, Mp}}, L.dX1, Cp, R, Cp, o));
       CK(gemm_nt(st, dt, {{L.dpre, Mp, opp(e, k, Cp, 0), Mp, Mp}}, L.dX2, Cp, R, Cp, o));
       GemmOpt v; v.n_valid = Rr;
-      CK(gemm_nt(st, DT_F32, {{L.dsb, Mp, opp(e, fmt("fusl_%s.n", lv)), Mp, Mp}}, L.dvl, Cp, B, Cp, v)); }
+      CK(hand());
+      CK(gemm_nt(ls, DT_F32, {{L.dsb, Mp, opp(e, fmt("fusl_%s.n", lv)), Mp, Mp}}, L.dvl, Cp, B, Cp, v)); }
     // -- spa_graph / graph_conv
     { const float scale = 1.0f / sqrtf((float)C);
       const std::string ln1 = fmt("gconv_feat_ln_spa_graph_%s", lv), ln2 = fmt("gconv_update_ln_spa_graph_%s", lv);
@@ -1342,18 +1381,19 @@ int level_bwd(E* e, hipStream_t st, int li, const float* target) {
       else CK(gemm_nt(st, dt, {{L.dA0_t, Tp, L.PTt, B * Tp, Tp, (int64_t)N * Tp, (int64_t)Tp}}, L.dX1, Cp, N, Cp, a0));
       TnOpt pt = zt; pt.alpha = scale;
       CK(gemm_tn(e, st, dt, L.dA0_t, Tp, Tp, L.X1, Cp, Cp, L.dPT, Cp, N, T, C, OFF0, pt));
-      CK(colsum(st, DT_F32, L.dA0, R, Tp, Tp, T, nullptr, nullptr, nullptr, ACT_NONE, L.dk0s, Tp, N));
+      CK(hand());
+      CK(colsum(ls, DT_F32, L.dA0, R, Tp, Tp, T, nullptr, nullptr, nullptr, ACT_NONE, L.dk0s, Tp, N));
       // k0s = scale * Wd . b_t2 ; PT = Wd . W_t2^T
-      CK(cmpc_wcolsum(DT_F32, L.Wd, L.dk0s, gptr(e, fmt("spa_graph_trans2_%s/biases", lv)), 0, 1, B * Tp, Cp, C, scale, st));
-      CK(gemm_nt(st, DT_F32, {{L.dPT, Cp, opp(e, fmt("t2_%s.t", lv)), Cp, Cp}}, L.dWd, Cp, B * Tp, Cp, o));
-      CK(gemm_tn(e, st, DT_F32, L.dPT, Cp, Cp, L.Wd, Cp, Cp, gptr(e, fmt("spa_graph_trans2_%s/DW", lv)), C, B * Tp, C, C, OFF0, d));
-      CK(cmpc_rank1_update(DT_F32, L.dWd, L.dk0s, pptr(e, fmt("spa_graph_trans2_%s/biases", lv)), nullptr, nullptr, 0, scale, 0.0f, 1, B * Tp, Cp, C, st));
+      CK(cmpc_wcolsum(DT_F32, L.Wd, L.dk0s, gptr(e, fmt("spa_graph_trans2_%s/biases", lv)), 0, 1, B * Tp, Cp, C, scale, ls));
+      CK(gemm_nt(ls, DT_F32, {{L.dPT, Cp, opp(e, fmt("t2_%s.t", lv)), Cp, Cp}}, L.dWd, Cp, B * Tp, Cp, o));
+      CK(gemm_tn(e, ls, DT_F32, L.dPT, Cp, Cp, L.Wd, Cp, Cp, gptr(e, fmt("spa_graph_trans2_%s/DW", lv)), C, B * Tp, C, C, OFF0, d));
+      CK(cmpc_rank1_update(DT_F32, L.dWd, L.dk0s, pptr(e, fmt("spa_graph_trans2_%s/biases", lv)), nullptr, nullptr, 0, scale, 0.0f, 1, B * Tp, Cp, C, ls));
       // Wd = wf . W_w + b_w   (rows t < T of every sample; pad rows of dWd are zero)
-      CK(colsum(st, DT_F32, L.dWd, B * Tp, Cp, Cp, C, gptr(e, fmt("words_trans_%s/biases", lv))));
+      CK(colsum(ls, DT_F32, L.dWd, B * Tp, Cp, Cp, C, gptr(e, fmt("words_trans_%s/biases", lv))));
       TnOpt ww; ww.nb2 = B; ww.a_bs = (int64_t)T * Cp; ww.d_bs = (int64_t)Tp * Cp; ww.o_bs = 0; ww.defer = true;
-      CK(gemm_tn(e, st, DT_F32, e->wf, Cp, Cp, L.dWd, Cp, Cp, gptr(e, fmt("words_trans_%s/DW", lv)), C, T, C, C, OFF0, ww));
+      CK(gemm_tn(e, ls, DT_F32, e->wf, Cp, Cp, L.dWd, Cp, Cp, gptr(e, fmt("words_trans_%s/DW", lv)), C, T, C, C, OFF0, ww));
       GemmOpt dw; dw.n_valid = C; dw.batch = B; dw.sC = (int64_t)T * Cp;
-      CK(gemm_nt(st, DT_F32, {{L.dWd, Cp, opp(e, fmt("wtrans_%s.n", lv)), Cp, Cp, (int64_t)Tp * Cp, 0}}, L.dwf, Cp, T, Cp, dw)); }
+      CK(gemm_nt(ls, DT_F32, {{L.dWd, Cp, opp(e, fmt("wtrans_%s.n", lv)), Cp, Cp, (int64_t)Tp * Cp, 0}}, L.dwf, Cp, T, Cp, dw)); }
     // -- mutan
     { CK(cmpc_mutan_bwd(dt, L.P, L.g, L.X1, L.mut_rstd, L.dX1, L.dg, B, N, Cp, C, st));
       void* dP = L.P;                         // overwritten in place
@@ -1372,16 +1412,17 @@ int level_bwd(E* e, hipStream_t st, int li, const float* target) {
       else CK(gemm_tn(e, st, dt, e->spatial, 64, 64, dP, 5 * Cp, Cp, gwv, C, R, e->sp, C, os, d));
       GemmOpt o; o.n_valid = C;
       CK(gemm_nt(st, dt, {{dP, 5 * Cp, opp(e, fmt("mutan_%s.n", lv)), 5 * Cp, 5 * Cp}}, L.dX0, Cp, R, Cp, o));
+      CK(hand());
       const int64_t base_l = poff(e, fmt("lang_trans_%s_head1/DW", lv));
       Offs ol;
       for (int hd = 0; hd < 5; ++hd) {
-          CK(colsum(st, DT_F32, L.dg + (size_t)hd * Cp, B, 5 * Cp, Cp, C, gptr(e, fmt("lang_trans_%s_head%d/biases", lv, hd + 1)),
+          CK(colsum(ls, DT_F32, L.dg + (size_t)hd * Cp, B, 5 * Cp, Cp, C, gptr(e, fmt("lang_trans_%s_head%d/biases", lv, hd + 1)),
                     L.g + (size_t)hd * Cp, L.dg + (size_t)hd * Cp, ACT_TANH));
           ol.push_back({0, (int64_t)hd * Cp, poff(e, fmt("lang_trans_%s_head%d/DW", lv, hd + 1)) - base_l});
       }
-      CK(gemm_tn(e, st, DT_F32, e->vl, Cp, Cp, L.dg, 5 * Cp, Cp, gptr(e, fmt("lang_trans_%s_head1/DW", lv)), C, B, Rr, C, ol, d));
+      CK(gemm_tn(e, ls, DT_F32, e->vl, Cp, Cp, L.dg, 5 * Cp, Cp, gptr(e, fmt("lang_trans_%s_head1/DW", lv)), C, B, Rr, C, ol, d));
       GemmOpt v; v.n_valid = Rr; v.accumulate = 1;          // on top of fusion's share
-      CK(gemm_nt(st, DT_F32, {{L.dg, 5 * Cp, opp(e, fmt("mlang_%s.n", lv)), 5 * Cp, 5 * Cp}}, L.dvl, Cp, B, Cp, v)); }
+      CK(gemm_nt(ls, DT_F32, {{L.dg, 5 * Cp, opp(e, fmt("mlang_%s.n", lv)), 5 * Cp, 5 * Cp}}, L.dvl, Cp, B, Cp, v)); }
     // -- lateral
     CK(cmpc_l2norm_rows_bwd(dt, L.dX0, L.X0, L.lat_rstd, L.dV, R, Cp, C, 0, st));
     if (!e->lat_tanh) CK(colsum(st, dt, L.dV, R, Cp, Cp, C, gptr(e, fmt("%s_lateral/biases", lv))));
@@ -1683,13 +1724,15 @@ int exchange_lang_fwd(E* e, hipStream_t st, int xi) {
     GemmOpt k; k.n_valid = M;
     return gemm_nt(st, DT_F32, {{X.q, Mp, opp(e, fmt("key_%s.n", lv)), Mp, Mp}}, X.kq, Mp, B, Mp, k);
 }
+// A module's forward in three parts, so that the caller can keep the paired trans_feat product (which reads only the round's inputs
+// f1, f2) off the module's serial chain: exchange_attn_fwd (attention pooling -> gv -> the two gates, ~8 small launches on `feat`),
+// exchange_trans_fwd (the 1x1 convs of f1 / f2, one launch), exchange_combine_fwd (reads both).  Same kernels and grids as one chain.
 // f2 == nullptr: one gated branch (CMPCv5_BiLSTM_model.py:343-346); gv_tanh: tanh before the all-dims l2_normalize of gv_lang (v5:328-329,
 // not in CMPCv5_model.py:318)
-int exchange_fwd(E* e, hipStream_t st, int xi, const void* feat, const void* f1, const void* f2) {
+int exchange_attn_fwd(E* e, hipStream_t st, int xi, const void* feat, int nbr) {
     ExgBuf& X = e->ex[xi]; const char* lv = exn(e, xi);
-    const int B = e->B, N = e->N, R = e->R, Cp = e->Cp, M = e->M, Mp = e->Mp, dt = e->dt;
+    const int B = e->B, N = e->N, Cp = e->Cp, M = e->M, Mp = e->Mp, dt = e->dt;
     const float s = 1.0f / sqrtf((float)M);
-    const int nbr = f2 ? 2 : 1;
     CK(cmpc_rowdot1(dt, feat, X.kq, Mp, X.logits, B, N, Mp, M, s, st));
     CK(cmpc_softmax_n_fwd(X.logits, X.attn, B, N, st));
     CK(cmpc_wcolsum(dt, feat, X.attn, X.pooled, Mp, B, N, Mp, M, 1.0f, st));
@@ -1697,62 +1740,126 @@ int exchange_fwd(E* e, hipStream_t st, int xi, const void* feat, const void* f1,
     GemmOpt g; g.n_valid = M; g.bias = pptr(e, fmt("gv_lang_%sgv_f1/biases", lv)); if (e->gv_tanh) g.act = ACT_TANH;
     CK(gemm_nt(st, DT_F32, {{X.pooled, Mp, opp(e, gvk), ldk, Mp}, {e->nec, Cp, opp(e, gvk, 0, Mp), ldk, Cp}}, X.gvpre, Mp, B, Mp, g));
     CK(cmpc_l2norm_all_fwd(X.gvpre, X.gv, X.rs1, B * Mp, st));
-    const void* fx[2] = {f1, f2}; const char* fn[2] = {"f1", "f2"};
-    NtJob tj[2];
+    const char* fn[2] = {"f1", "f2"};
     for (int i = 0; i < nbr; ++i) {
         GemmOpt a; a.n_valid = M; a.bias = pptr(e, fmt("lang_feat_%s_%s/biases", lv, fn[i])); a.act = ACT_SIGMOID;
         CK(gemm_nt(st, DT_F32, {{X.gv, Mp, opp(e, fmt("lfeat_%s_%s.t", lv, fn[i])), Mp, Mp}}, X.g[i], Mp, B, Mp, a));
+    }
+    return CMPC_OK;
+}
+int exchange_trans_fwd(E* e, hipStream_t st, int xi, const void* f1, const void* f2) {
+    ExgBuf& X = e->ex[xi]; const char* lv = exn(e, xi);
+    const int R = e->R, M = e->M, Mp = e->Mp, dt = e->dt;
+    const int nbr = f2 ? 2 : 1;
+    const void* fx[2] = {f1, f2}; const char* fn[2] = {"f1", "f2"};
+    NtJob tj[2];
+    for (int i = 0; i < nbr; ++i) {
         GemmOpt b; b.n_valid = M; b.bias = pptr(e, fmt("trans_feat_%s_%s/biases", lv, fn[i])); b.act = ACT_RELU;
         tj[i] = NtJob{Seg{fx[i], Mp, opp(e, fmt("tfeat_%s_%s.t", lv, fn[i])), Mp, Mp}, X.r[i], Mp, b};
     }
-    if (nbr == 2) CK(gemm_nt_pair(st, dt, tj[0], tj[1], R, Mp));         // the two trans_feat 1x1 convs: one launch
-    else CK(gemm_nt(st, dt, {tj[0].seg}, tj[0].C, tj[0].ldc, R, Mp, tj[0].o));
-    return cmpc_exchange_combine_fwd(dt, feat, X.r[0], nbr == 2 ? X.r[1] : nullptr, X.g[0], nbr == 2 ? X.g[1] : nullptr, Mp, X.out, X.rstd, B, N, Mp, M, st);
+    if (nbr == 2) return gemm_nt_pair(st, dt, tj[0], tj[1], R, Mp);         // the two trans_feat 1x1 convs: one launch
+    return gemm_nt(st, dt, {tj[0].seg}, tj[0].C, tj[0].ldc, R, Mp, tj[0].o);
 }
-// outputs: X.dfeat, X.dfs[0] (d f1), X.dfs[1] (d f2), X.dnec
-int exchange_bwd(E* e, hipStream_t st, int xi, const void* dout, const void* feat, const void* f1, const void* f2) {
+int exchange_combine_fwd(E* e, hipStream_t st, int xi, const void* feat, int nbr) {
+    ExgBuf& X = e->ex[xi];
+    return cmpc_exchange_combine_fwd(e->dt, feat, X.r[0], nbr == 2 ? X.r[1] : nullptr, X.g[0], nbr == 2 ? X.g[1] : nullptr, e->Mp, X.out, X.rstd,
+                                     e->B, e->N, e->Mp, e->M, st);
+}
+// One round of NX modules: the products go to `main` (idle between the fork and the join of a round), in module order, an event behind
+// each; lane i runs module i's attention chain and waits for its product before the combine.  With one lane every stream is `main` and
+// the issue order below is the serial order.  done[i] (optional): recorded behind module i's combine.
+int exchange_round_fwd(E* e, hipStream_t main, hipStream_t (&st)[3], int base, const void* (&in)[3], hipEvent_t* done) {
+    const int NX = e->nex, nbr = NX > 2 ? 2 : 1;
+    const int o1[3] = {1, 0, 0}, o2[3] = {2, 2, 1};
+    const bool lanes = e->cfg.n_lanes > 1;
+    hipEvent_t prod[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < NX; ++i) {
+        CK(exchange_trans_fwd(e, main, base + i, in[o1[i]], NX > 2 ? in[o2[i]] : nullptr));
+        if (lanes) { prod[i] = next_event(e); HCK(hipEventRecord(prod[i], main)); }
+    }
+    for (int i = 0; i < NX; ++i) {
+        CK(exchange_attn_fwd(e, st[i], base + i, in[i], nbr));
+        if (prod[i]) HCK(hipStreamWaitEvent(st[i], prod[i], 0));
+        CK(exchange_combine_fwd(e, st[i], base + i, in[i], nbr));
+        if (done && lanes) { done[i] = next_event(e); HCK(hipEventRecord(done[i], st[i])); }
+    }
+    return CMPC_OK;
+}
+
+// A module's backward in four launch groups plus its host-only registrations (exchange_defer_dw), so that the caller can keep on the
+// module's serial chain only what the next stage on that chain reads:
+//   (a) exchange_combine_bwd_   -> X.dp, X.dg, (X.dfeat, first term)
+//   (b) exchange_dx_bwd         -> X.dfs[0] (d f1), X.dfs[1] (d f2): the paired product, needs (a) only
+//   (c) exchange_feat_bwd       -> X.dfeat complete (ends at rank1_update), needs (a)
+//   (d) exchange_lang_bwd       -> X.dnec, X.dq, X.dkq: the text side, read much later; needs (c)
+// Same kernels, grids and per-buffer write order as the former single chain (X.dnec: the gv product, then the accumulating query one).
+int exchange_combine_bwd_(E* e, hipStream_t st, int xi, const void* dout, int nbr) {
     ExgBuf& X = e->ex[xi]; const char* lv = exn(e, xi);
-    const int B = e->B, N = e->N, R = e->R, Cp = e->Cp, M = e->M, Mp = e->Mp, dt = e->dt, Rr = e->RNN;
-    const float s = 1.0f / sqrtf((float)M);
-    const int nbr = f2 ? 2 : 1;
-    TnOpt d; d.defer = true;
-    CK(cmpc_exchange_combine_bwd(dt, dout, X.out, X.rstd, X.r[0], nbr == 2 ? X.r[1] : nullptr, X.g[0], nbr == 2 ? X.g[1] : nullptr, Mp, X.dfeat, 0,
-                                 X.dp[0], nbr == 2 ? X.dp[1] : nullptr, X.dg[0], nbr == 2 ? X.dg[1] : nullptr,
-                                 gptr(e, fmt("trans_feat_%s_f1/biases", lv)), nbr == 2 ? gptr(e, fmt("trans_feat_%s_f2/biases", lv)) : nullptr, B, N, Mp, M, st));
-    const void* fx[2] = {f1, f2}; const char* fn[2] = {"f1", "f2"};
+    return cmpc_exchange_combine_bwd(e->dt, dout, X.out, X.rstd, X.r[0], nbr == 2 ? X.r[1] : nullptr, X.g[0], nbr == 2 ? X.g[1] : nullptr, e->Mp, X.dfeat, 0,
+                                     X.dp[0], nbr == 2 ? X.dp[1] : nullptr, X.dg[0], nbr == 2 ? X.dg[1] : nullptr,
+                                     gptr(e, fmt("trans_feat_%s_f1/biases", lv)), nbr == 2 ? gptr(e, fmt("trans_feat_%s_f2/biases", lv)) : nullptr,
+                                     e->B, e->N, e->Mp, e->M, st);
+}
+int exchange_dx_bwd(E* e, hipStream_t st, int xi, int nbr) {
+    ExgBuf& X = e->ex[xi]; const char* lv = exn(e, xi);
+    const int R = e->R, M = e->M, Mp = e->Mp, dt = e->dt;
+    const char* fn[2] = {"f1", "f2"};
     NtJob dj[2];
     for (int i = 0; i < nbr; ++i) {
-        CK(gemm_tn(e, st, dt, fx[i], Mp, Mp, X.dp[i], Mp, Mp, gptr(e, fmt("trans_feat_%s_%s/DW", lv, fn[i])), M, R, M, M, OFF0, d));
         GemmOpt o; o.n_valid = M;
         dj[i] = NtJob{Seg{X.dp[i], Mp, opp(e, fmt("tfeat_%s_%s.n", lv, fn[i])), Mp, Mp}, X.dfs[i], Mp, o};
-        if (nbr == 2 && i == 1) CK(gemm_nt_pair(st, dt, dj[0], dj[1], R, Mp));       // d f1 and d f2: one launch
-        if (nbr == 1) CK(gemm_nt(st, dt, {dj[0].seg}, dj[0].C, dj[0].ldc, R, Mp, dj[0].o));
+    }
+    if (nbr == 2) return gemm_nt_pair(st, dt, dj[0], dj[1], R, Mp);       // d f1 and d f2: one launch
+    return gemm_nt(st, dt, {dj[0].seg}, dj[0].C, dj[0].ldc, R, Mp, dj[0].o);
+}
+int exchange_feat_bwd(E* e, hipStream_t st, int xi, const void* feat, int nbr) {
+    ExgBuf& X = e->ex[xi]; const char* lv = exn(e, xi);
+    const int B = e->B, N = e->N, M = e->M, Mp = e->Mp, dt = e->dt;
+    const float s = 1.0f / sqrtf((float)M);
+    const char* fn[2] = {"f1", "f2"};
+    for (int i = 0; i < nbr; ++i) {
         CK(colsum(st, DT_F32, X.dg[i], B, Mp, Mp, M, gptr(e, fmt("lang_feat_%s_%s/biases", lv, fn[i])), X.g[i], X.dg[i], ACT_SIGMOID));
-        CK(gemm_tn(e, st, DT_F32, X.gv, Mp, Mp, X.dg[i], Mp, Mp, gptr(e, fmt("lang_feat_%s_%s/DW", lv, fn[i])), M, B, M, M, OFF0, d));
         GemmOpt a; a.n_valid = M; a.accumulate = i == 1;
         CK(gemm_nt(st, DT_F32, {{X.dg[i], Mp, opp(e, fmt("lfeat_%s_%s.n", lv, fn[i])), Mp, Mp}}, X.dgv, Mp, B, Mp, a));
     }
     CK(cmpc_l2norm_all_bwd(X.dgv, X.gv, X.rs1, X.dgvpre, B * Mp, st));
     if (!e->gv_tanh) CK(colsum(st, DT_F32, X.dgvpre, B, Mp, Mp, M, gptr(e, fmt("gv_lang_%sgv_f1/biases", lv))));
     else CK(colsum(st, DT_F32, X.dgvpre, B, Mp, Mp, M, gptr(e, fmt("gv_lang_%sgv_f1/biases", lv)), X.gvpre, X.dgvpre, ACT_TANH));     // X.gvpre holds tanh(...)
-    float* gwg = gptr(e, fmt("gv_lang_%sgv_f1/DW", lv));
-    CK(gemm_tn(e, st, DT_F32, X.pooled, Mp, Mp, X.dgvpre, Mp, Mp, gwg, M, B, M, M, OFF0, d));
-    CK(gemm_tn(e, st, DT_F32, e->nec, Cp, Cp, X.dgvpre, Mp, Mp, gwg + (size_t)M * M, M, B, Rr, M, OFF0, d));
-    const std::string gvn = fmt("gv_%s.n", lv);
     GemmOpt m; m.n_valid = M;
-    CK(gemm_nt(st, DT_F32, {{X.dgvpre, Mp, opp(e, gvn), Mp, Mp}}, X.dpooled, Mp, B, Mp, m));
-    GemmOpt r; r.n_valid = Rr;
-    CK(gemm_nt(st, DT_F32, {{X.dgvpre, Mp, opp(e, gvn, Mp, 0), Mp, Mp}}, X.dnec, Cp, B, Cp, r));
+    CK(gemm_nt(st, DT_F32, {{X.dgvpre, Mp, opp(e, fmt("gv_%s.n", lv)), Mp, Mp}}, X.dpooled, Mp, B, Mp, m));
     CK(cmpc_rowdot1(dt, feat, X.dpooled, Mp, X.dattn, B, N, Mp, M, 1.0f, st));
     CK(cmpc_softmax_n_bwd(X.dattn, X.attn, X.dlog, B, N, st));
-    CK(cmpc_rank1_update(dt, X.dfeat, X.attn, X.dpooled, X.dlog, X.kq, Mp, 1.0f, s, B, N, Mp, M, st));
+    return cmpc_rank1_update(dt, X.dfeat, X.attn, X.dpooled, X.dlog, X.kq, Mp, 1.0f, s, B, N, Mp, M, st);
+}
+int exchange_lang_bwd(E* e, hipStream_t st, int xi, const void* feat) {
+    ExgBuf& X = e->ex[xi]; const char* lv = exn(e, xi);
+    const int B = e->B, N = e->N, Cp = e->Cp, M = e->M, Mp = e->Mp, dt = e->dt, Rr = e->RNN;
+    const float s = 1.0f / sqrtf((float)M);
+    GemmOpt r; r.n_valid = Rr;
+    CK(gemm_nt(st, DT_F32, {{X.dgvpre, Mp, opp(e, fmt("gv_%s.n", lv), Mp, 0), Mp, Mp}}, X.dnec, Cp, B, Cp, r));
     CK(cmpc_wcolsum(dt, feat, X.dlog, X.dkq, Mp, B, N, Mp, M, s, st));
+    GemmOpt m; m.n_valid = M;
     CK(gemm_nt(st, DT_F32, {{X.dkq, Mp, opp(e, fmt("key_%s.t", lv)), Mp, Mp}}, X.dq, Mp, B, Mp, m));
-    CK(gemm_tn(e, st, DT_F32, X.dkq, Mp, Mp, X.q, Mp, Mp, gptr(e, fmt("spa_graph_key_%sgv_f1/DW", lv)), M, B, M, M, OFF0, d));
     CK(colsum(st, DT_F32, X.dq, B, Mp, Mp, M, gptr(e, fmt("lang_query_%sgv_f1/biases", lv))));
-    CK(gemm_tn(e, st, DT_F32, e->nec, Cp, Cp, X.dq, Mp, Mp, gptr(e, fmt("lang_query_%sgv_f1/DW", lv)), M, B, Rr, M, OFF0, d));
     GemmOpt n; n.n_valid = Rr; n.accumulate = 1;
     return gemm_nt(st, DT_F32, {{X.dq, Mp, opp(e, fmt("query_%s.n", lv)), Mp, Mp}}, X.dnec, Cp, B, Cp, n);
+}
+// the module's weight-gradient products, registered for the bucket's grouped launch (host only; the order of the former single chain)
+int exchange_defer_dw(E* e, int xi, const void* f1, const void* f2) {
+    ExgBuf& X = e->ex[xi]; const char* lv = exn(e, xi);
+    const int B = e->B, R = e->R, Cp = e->Cp, M = e->M, Mp = e->Mp, dt = e->dt, Rr = e->RNN;
+    const int nbr = f2 ? 2 : 1;
+    TnOpt d; d.defer = true;
+    const void* fx[2] = {f1, f2}; const char* fn[2] = {"f1", "f2"};
+    for (int i = 0; i < nbr; ++i) {
+        CK(gemm_tn(e, nullptr, dt, fx[i], Mp, Mp, X.dp[i], Mp, Mp, gptr(e, fmt("trans_feat_%s_%s/DW", lv, fn[i])), M, R, M, M, OFF0, d));
+        CK(gemm_tn(e, nullptr, DT_F32, X.gv, Mp, Mp, X.dg[i], Mp, Mp, gptr(e, fmt("lang_feat_%s_%s/DW", lv, fn[i])), M, B, M, M, OFF0, d));
+    }
+    float* gwg = gptr(e, fmt("gv_lang_%sgv_f1/DW", lv));
+    CK(gemm_tn(e, nullptr, DT_F32, X.pooled, Mp, Mp, X.dgvpre, Mp, Mp, gwg, M, B, M, M, OFF0, d));
+    CK(gemm_tn(e, nullptr, DT_F32, e->nec, Cp, Cp, X.dgvpre, Mp, Mp, gwg + (size_t)M * M, M, B, Rr, M, OFF0, d));
+    CK(gemm_tn(e, nullptr, DT_F32, X.dkq, Mp, Mp, X.q, Mp, Mp, gptr(e, fmt("spa_graph_key_%sgv_f1/DW", lv)), M, B, M, M, OFF0, d));
+    return gemm_tn(e, nullptr, DT_F32, e->nec, Cp, Cp, X.dq, Mp, Mp, gptr(e, fmt("lang_query_%sgv_f1/DW", lv)), M, B, Rr, M, OFF0, d);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1797,9 +1904,9 @@ int clstm_bwd(E* e, hipStream_t st, hipEvent_t* dx_ready) {
         ClstmStep& S = e->cl[s];
         const void* h_prev = s > 0 ? e->cl[s - 1].h_new : nullptr;
         const void* c_prev = s > 0 ? e->cl[s - 1].c_new : nullptr;
-        CK(cmpc_convlstm_bwd(dt, dh, dc, S.Yg, c_prev, S.c_pre, pptr(e, pre + "W_ci"), pptr(e, pre + "W_cf"), pptr(e, pre + "W_co"), &ln, S.sums,
-                             S.dYg, s > 0 ? S.dc_prev : nullptr, gptr(e, pre + "W_ci"), gptr(e, pre + "W_cf"), gptr(e, pre + "W_co"), &dln,
-                             e->cl_scr, e->cl_bs, B, N, Mp, M, st));
+        // passes 1-3 only: the peephole gradient of the step (gradient-buffer rows, read by nothing before the optimizer) follows the loop
+        CK(cmpc_convlstm_bwd_gates(dt, dh, dc, S.Yg, c_prev, S.c_pre, pptr(e, pre + "W_ci"), pptr(e, pre + "W_cf"), pptr(e, pre + "W_co"), &ln, S.sums,
+                                   S.dYg, s > 0 ? S.dc_prev : nullptr, &dln, e->cl_scr, e->cl_bs, B, N, Mp, M, st));
         Offs ox, oh;
         for (int g = 0; g < 4; ++g) { ox.push_back({0, (int64_t)g * Mp, (int64_t)g * M}); oh.push_back({0, (int64_t)g * Mp, (int64_t)M * 4 * M + (int64_t)g * M}); }
         CK(gemm_tn(e, st, dt, xs[s], Mp, Mp, S.dYg, 4 * Mp, Mp, gk, 4 * M, R, M, M, ox, d));
@@ -1820,6 +1927,19 @@ int clstm_bwd(E* e, hipStream_t st, hipEvent_t* dx_ready) {
         }
         CK(gemm_nt(xst, dt, {{S.dYg, 4 * Mp, opp(e, "clstm.n"), 4 * Mp, 4 * Mp}}, S.dx, Mp, R, Mp, o));
         if (dx_ready && dx_ready[s]) HCK(hipEventRecord(dx_ready[s], xst));
+    }
+    return CMPC_OK;
+}
+// the three peephole launches of clstm_bwd, kept off the recurrence's chain: one stream, in the steps' order (they add into the same
+// rows without atomics), anywhere behind the chain and before the flush of the ConvLSTM's bucket.  They read each step's finished dYg,
+// which stays in place for the deferred weight-gradient products anyway
+int clstm_peephole_bwd(E* e, hipStream_t st) {
+    const int B = e->B, N = e->N, M = e->M, Mp = e->Mp, dt = e->dt;
+    const std::string pre = "rnn/conv_lstm_cell/";
+    for (int s = e->ncl - 1; s >= 0; --s) {
+        ClstmStep& S = e->cl[s];
+        CK(cmpc_convlstm_peephole_grad(dt, S.dYg, s > 0 ? e->cl[s - 1].c_new : nullptr, S.c_pre, gptr(e, pre + "W_ci"), gptr(e, pre + "W_cf"),
+                                       gptr(e, pre + "W_co"), B, N, Mp, M, st));
     }
     return CMPC_OK;
 }
@@ -1963,21 +2083,28 @@ int aspp_decoder_bwd(E* e, hipStream_t main, const float* target) {
     return cmpc_rank1_update(dt, e->dfused, e->ones_n, e->dpooled, nullptr, nullptr, Mp, 1.0f, 0.0f, B, N, Mp, M, main);
 }
 
-// bucket b is complete: its deferred weight-gradient products in one grouped launch, its deferred bias / LayerNorm / peephole folds in
-// another, then the event a data-parallel caller waits on before all-reducing the bucket
-int flush_bucket(E* e, hipStream_t st, int b) {
+// bucket b is complete: its deferred weight-gradient products in one grouped launch (flush_bucket_dw), its deferred bias / LayerNorm /
+// peephole folds in another, then the event a data-parallel caller waits on before all-reducing the bucket (flush_bucket_folds).  The
+// two halves may be issued apart (the text bucket's products have their operands long before its last fold is registered): the
+// stream of the second must then be ordered behind the first.
+int flush_bucket_dw(E* e, hipStream_t st, int b) {
     std::vector<cmpc_gemm_tn_args>& d = e->deferred[b];
-    if (!d.empty()) {
-        const int rc = cmpc_gemm_tn_grouped_cached(d.data(), (int)d.size(), e->tn_table[b], 4, &e->tn_victim[b], e->tn_table_bytes, e->tn_shadow[b], st);
-        d.clear();
-        CK(rc);
-    }
+    if (d.empty()) return CMPC_OK;
+    const int rc = cmpc_gemm_tn_grouped_cached(d.data(), (int)d.size(), e->tn_table[b], 4, &e->tn_victim[b], e->tn_table_bytes, e->tn_shadow[b], st);
+    d.clear();
+    return rc;
+}
+int flush_bucket_folds(E* e, hipStream_t st, int b) {
     const float* lo[4]; const float* hi[4];
     int nr = 0;
     for (const E::Range& r : e->bucket[b]) { lo[nr] = e->grads + r.off; hi[nr] = e->grads + r.off + r.count; ++nr; }
     CK(cmpc_fold_flush_ranges(&e->fold, lo, hi, nr, e->fold_table[b], e->fold_shadow[b].data(), &e->fold_shadow_n[b], st));
     HCK(hipEventRecord(e->bucket_ev[b], st));
     return CMPC_OK;
+}
+int flush_bucket(E* e, hipStream_t st, int b) {
+    CK(flush_bucket_dw(e, st, b));
+    return flush_bucket_folds(e, st, b);
 }
 
 int params_ready(E* e, hipStream_t st, int stage) {
@@ -2202,7 +2329,7 @@ extern "C" int cmpc_create(const cmpc_cfg* c, cmpc_handle* out) {
         ECK(hipMemcpy(e->ones_n, on.data(), on.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     for (auto& s : e->lane) ECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    e->evpool.resize(256);
+    e->evpool.resize(512);      // a train step takes 60-65 (forward 18-20, backward 40-45) and two steps can be in flight
     for (auto& ev : e->evpool) { ev = nullptr; ECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); }
     ECK(hipEventCreateWithFlags(&e->ev_opt0, hipEventDisableTiming));
     ECK(hipEventCreateWithFlags(&e->ev_opt1, hipEventDisableTiming));
@@ -2535,19 +2662,18 @@ extern "C" int cmpc_forward(cmpc_handle e, const cmpc_feeds* f, const cmpc_fetch
     if (f->levels_done) HCK(hipEventRecord((hipEvent_t)f->levels_done, main));
     // gated_exchange_fusion_lstm_2times (CMPC_model.py:261-293: modules c3, c4, c5 = lv[2], lv[1], lv[0], each reading the other two;
     // CMPCv5_BiLSTM_model.py:349-388: modules c4, c5 = lv[1], lv[0], each reading the other one)
+    // Per round: the lanes run the modules' attention chains; `main`, otherwise idle between the fork and the join, carries the three
+    // paired trans_feat products (exchange_round_fwd).
     const void* fz[3] = {e->lv[NL - 1].F, e->lv[NL - 2].F, NL > 2 ? e->lv[0].F : nullptr};
-    const int o1[3] = {1, 0, 0}, o2[3] = {2, 2, 1};
     CK(fork_lanes(e, main, st));
-    for (int i = 0; i < NX; ++i) CK(exchange_fwd(e, st[i], i, fz[i], fz[o1[i]], NX > 2 ? fz[o2[i]] : nullptr));
+    CK(exchange_round_fwd(e, main, st, 0, fz, nullptr));
     CK(join_lanes(e, main));
     CK(mark(e, "fwd:exch1_done", main));
     const void* ez[3] = {e->ex[0].out, e->ex[1].out, NX > 2 ? e->ex[2].out : nullptr};
     CK(fork_lanes(e, main, st));
     hipEvent_t ex2_done[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < NX; ++i) {
-        CK(exchange_fwd(e, st[i], NX + i, ez[i], ez[o1[i]], NX > 2 ? ez[o2[i]] : nullptr));
-        if (e->cfg.n_lanes > 1) { ex2_done[i] = next_event(e); HCK(hipEventRecord(ex2_done[i], st[i])); }
-    }
+    CK(exchange_round_fwd(e, main, st, NX, ez, ex2_done));
+    CK(mark(e, "fwd:exch2_done", st[0]));        // module 0 feeds the first ConvLSTM step
     if (e->v5 && e->cfg.n_lanes > 1) { hipEvent_t ev = next_event(e); HCK(hipEventRecord(ev, e->lane[2])); HCK(hipStreamWaitEvent(main, ev, 0)); }   // the low-level branch
     CK(clstm_fwd(e, main, ex2_done));            // ConvLSTM step s only waits for the round-2 module s that feeds it
     CK(mark(e, "fwd:clstm_done", main));
@@ -2637,20 +2763,36 @@ extern "C" int cmpc_backward(cmpc_handle e, void* stream) {
     const int o1[3] = {1, 0, 0}, o2[3] = {2, 2, 1};
     const void* fz[3] = {e->lv[NL - 1].F, e->lv[NL - 2].F, NL > 2 ? e->lv[0].F : nullptr};
     const void* ez[3] = {e->ex[0].out, e->ex[1].out, NX > 2 ? e->ex[2].out : nullptr};
+    const int nbr = NX > 2 ? 2 : 1;
+    const bool lanes = e->cfg.n_lanes > 1;
     hipStream_t st[3];
+    for (int i = 0; i < 3; ++i) st[i] = lanes ? e->lane[i] : main;
+    auto record = [&](hipEvent_t& ev, hipStream_t s) { if (!lanes) return hipSuccess; ev = next_event(e); return hipEventRecord(ev, s); };
+    auto wait = [&](hipStream_t s, hipEvent_t ev) { return ev ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; };
     // ConvLSTM backward (last step first, on main); the round-2 exchange module s starts on its lane as soon as step s has
     // produced its input gradient
     hipEvent_t dx_ready[3] = {nullptr, nullptr, nullptr};
-    if (e->cfg.n_lanes > 1) for (int i = 0; i < NX; ++i) dx_ready[i] = next_event(e);
+    if (lanes) for (int i = 0; i < NX; ++i) dx_ready[i] = next_event(e);
     CK(clstm_bwd(e, main, dx_ready));
     CK(mark(e, "bwd:clstm_done", main));
     HOSTPROF("clstm");
+    // Exchange round 2.  The lanes keep only what round 1 reads: (a) combine, (b) the paired dX product -> dfs, (c) the chain to dfeat.
+    // (d), the text side of each module, goes to `main` behind the ConvLSTM chain.  The host issue order is a valid serial order (one
+    // lane: every stream is `main`); each event is recorded before it is waited on.
+    hipEvent_t dfs2[3] = {nullptr, nullptr, nullptr}, feat2[3] = {nullptr, nullptr, nullptr};
     for (int i = 0; i < NX; ++i) {
-        st[i] = e->cfg.n_lanes > 1 ? e->lane[i] : main;
-        if (dx_ready[i]) HCK(hipStreamWaitEvent(st[i], dx_ready[i], 0));
-        CK(exchange_bwd(e, st[i], NX + i, e->cl[i].dx, ez[i], ez[o1[i]], NX > 2 ? ez[o2[i]] : nullptr));
+        HCK(wait(st[i], dx_ready[i]));
+        CK(exchange_combine_bwd_(e, st[i], NX + i, e->cl[i].dx, nbr));
+        CK(exchange_dx_bwd(e, st[i], NX + i, nbr));
+        HCK(record(dfs2[i], st[i]));
+        CK(exchange_feat_bwd(e, st[i], NX + i, ez[i], nbr));
+        HCK(record(feat2[i], st[i]));
     }
-    CK(join_lanes(e, main));
+    for (int i = NX - 1; i >= 0; --i) {          // the order in which the lanes finish
+        HCK(wait(main, feat2[i]));
+        CK(exchange_lang_bwd(e, main, NX + i, ez[i]));
+    }
+    for (int i = 0; i < NX; ++i) CK(exchange_defer_dw(e, NX + i, ez[o1[i]], NX > 2 ? ez[o2[i]] : nullptr));
     CK(mark(e, "bwd:exch2_done", main));
     HOSTPROF("exch2");
     // gradient of input j of a round = dfeat of module j + the f1 / f2 gradients of the modules that read it
@@ -2667,31 +2809,52 @@ extern "C" int cmpc_backward(cmpc_handle e, void* stream) {
     auto add_fan = [&](hipStream_t s, void* dst, const void* (&src)[3], int n) {
         return n == 3 ? add_n(s, dt, dst, {src[0], src[1], src[2]}, false, nmap) : add_n(s, dt, dst, {src[0], src[1]}, false, nmap);
     };
-    // exchange round 1
-    CK(fork_lanes(e, main, st));
+    // Exchange round 1.  Lane j waits for exactly what its fan-in reads (its own module's dfeat: stream order; the other modules' dfs)
+    // and runs (a), (c); `main` runs the three (b) products behind the (a) events, then the three (d) groups.
+    hipEvent_t comb1[3] = {nullptr, nullptr, nullptr}, feat1[3] = {nullptr, nullptr, nullptr}, dfs1[3] = {nullptr, nullptr, nullptr};
     for (int j = 0; j < NX; ++j) {
         const void* src[3];
         const int n = fan_in(NX, j, src);
         if (n != NX) { cmpc_set_error("backward: exchange fan-in"); return CMPC_EINVAL; }
+        for (int i = 0; i < NX; ++i) if (i != j) HCK(wait(st[j], dfs2[i]));
+        if (j == 0) CK(mark(e, "bwd:exch2_feat_done", st[0]));
         CK(add_fan(st[j], e->de1[j], src, n));
-        CK(exchange_bwd(e, st[j], j, e->de1[j], fz[j], fz[o1[j]], NX > 2 ? fz[o2[j]] : nullptr));
+        CK(exchange_combine_bwd_(e, st[j], j, e->de1[j], nbr));
+        HCK(record(comb1[j], st[j]));
+        CK(exchange_feat_bwd(e, st[j], j, fz[j], nbr));
+        HCK(record(feat1[j], st[j]));
     }
-    CK(join_lanes(e, main));
+    for (int j = 0; j < NX; ++j) {
+        HCK(wait(main, comb1[j]));
+        CK(exchange_dx_bwd(e, main, j, nbr));
+        HCK(record(dfs1[j], main));
+    }
+    for (int j = 0; j < NX; ++j) {
+        HCK(wait(main, feat1[j]));
+        CK(exchange_lang_bwd(e, main, j, fz[j]));
+    }
+    for (int j = 0; j < NX; ++j) CK(exchange_defer_dw(e, j, fz[o1[j]], NX > 2 ? fz[o2[j]] : nullptr));
     CK(mark(e, "bwd:exch1_done", main));
+    CK(clstm_peephole_bwd(e, main));      // behind the ConvLSTM chain (stream order) and off every chain: the levels start from events
     HOSTPROF("exch1");
-    // pyramid levels (lane i = level i = exchange input NL-1-i); the language-side sums run on main meanwhile, and so do
-    // the weight-gradient products of the bucket that has just become final (exchange modules, ConvLSTM, final score / ASPP + decoder):
-    // issued AFTER the fork, they run beside the levels instead of holding the lanes back
-    CK(fork_lanes(e, main, st));
+    // pyramid levels (lane i = level i = exchange input NL-1-i): each lane waits for the events its fan-in reads, not for `main`, which
+    // runs the language-side sums meanwhile (and, behind per-level events, the levels' own launches that feed only the text encoder's
+    // backward: level_bwd's `ls`), and the weight-gradient products of the bucket that has just become final (exchange
+    // modules, ConvLSTM, final score / ASPP + decoder): every producer of that bucket's operands and partial rows is behind an event
+    // `main` has waited on above (feat2[*], feat1[*]) or on `main` itself
     if (NX > 2) CK(add_n(main, DT_F32, e->dnec, {e->ex[0].dnec, e->ex[1].dnec, e->ex[2].dnec, e->ex[3].dnec, e->ex[4].dnec, e->ex[5].dnec}, false, (long)B * Cp));
     else CK(add_n(main, DT_F32, e->dnec, {e->ex[0].dnec, e->ex[1].dnec, e->ex[2].dnec, e->ex[3].dnec}, false, (long)B * Cp));
     if (!e->vid) CK(cmpc_lang_pool_bwd(e->dnec, e->nec, e->nec_rstd, e->parse, e->wf, e->dparse, e->dwf, B, T, Cp, e->RNN, 3, 0, e->NC, main));
     CK(flush_bucket(e, main, 0));
     for (int i = 0; i < NL; ++i) {
         const void* src[3];
-        const int n = fan_in(0, NL - 1 - i, src);
+        const int j = NL - 1 - i;
+        const int n = fan_in(0, j, src);
+        HCK(wait(st[i], feat1[j]));
+        for (int k = 0; k < NX; ++k) if (k != j) HCK(wait(st[i], dfs1[k]));
+        if (i == 0) CK(mark(e, "bwd:exch1_feat_done", st[0]));
         CK(add_fan(st[i], e->lv[i].dfus, src, n));
-        CK(e->vid ? level_bwd_video(e, st[i], i, target) : level_bwd(e, st[i], i, target));
+        CK(e->vid ? level_bwd_video(e, st[i], i, target) : level_bwd(e, st[i], i, target, main));
         const char* lvb[3] = {"bwd:level_c5_done", "bwd:level_c4_done", "bwd:level_c3_done"};
         CK(mark(e, lvb[i], st[i]));
     }
@@ -2730,11 +2893,14 @@ extern "C" int cmpc_backward(cmpc_handle e, void* stream) {
     if (NL > 2) CK(add_n(main, DT_F32, e->dwf, {e->lv[0].dwf, e->lv[1].dwf, e->lv[2].dwf}, true, (long)B * T * Cp));
     else CK(add_n(main, DT_F32, e->dwf, {e->lv[0].dwf, e->lv[1].dwf}, true, (long)B * T * Cp));
     CK(parser_bwd(e, main));
-    CK(text_bwd(e, main, e->seq_len_feed));
+    hipEvent_t text_dw = nullptr;
+    CK(text_bwd(e, main, e->seq_len_feed, wst, &text_dw));       // issues the text bucket's grouped products on wst, behind the levels' buckets
     CK(mark(e, "bwd:text_done", main));
     HOSTPROF("text");
     if (wg_done) HCK(hipStreamWaitEvent(main, wg_done, 0));
-    CK(flush_bucket(e, main, E::NBK - 1));     // text encoder + parser
+    if (text_dw) HCK(hipStreamWaitEvent(main, text_dw, 0));
+    if (!e->deferred[E::NBK - 1].empty()) { cmpc_set_error("backward: a text-bucket product was registered after the bucket's launch"); return CMPC_EINVAL; }
+    CK(flush_bucket_folds(e, main, E::NBK - 1));     // text encoder + parser: the folds, then the bucket's event
     CK(cmpc_fold_flush(&e->fold, main));       // (nothing is left; ends the collection)
     HCK(hipEventRecord(e->ev_grid_read, main));     // every read of the grid (the levels' dW products, joined above) is behind this point
     CK(mark(e, "bwd:end", main));

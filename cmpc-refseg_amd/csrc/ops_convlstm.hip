@@ -481,13 +481,12 @@ extern "C" int cmpc_convlstm_c(int dt, const void* Yg, const void* c_pre, const 
     return cmpc_check_launch("convlstm_c");
 }
 
-extern "C" int cmpc_convlstm_bwd(int dt, const void* dh, const void* dc_new, const void* Yg, const void* c_prev, const void* c_pre,
-                                 const float* W_ci, const float* W_cf, const float* W_co,
-                                 const cmpc_convlstm_ln* ln, const double* sums, void* dYg, void* dc_prev,
-                                 float* dW_ci, float* dW_cf, float* dW_co, const cmpc_convlstm_dln* dln, void* scr, double* bsums,
-                                 int B, int N, int ld, int M, void* stream) {
-    cmpc_op_scope op_("convlstm_bwd");
-    if (!ok("convlstm_bwd", dt, ld, M)) return CMPC_EINVAL;
+// passes 1-3 of the cell backward (everything the recurrence and the input gradient read); no launch check: the callers do it
+static int clstm_bwd_gates(int dt, const void* dh, const void* dc_new, const void* Yg, const void* c_prev, const void* c_pre,
+                           const float* W_ci, const float* W_cf, const float* W_co,
+                           const cmpc_convlstm_ln* ln, const double* sums, void* dYg, void* dc_prev,
+                           const cmpc_convlstm_dln* dln, void* scr, double* bsums,
+                           int B, int N, int ld, int M, void* stream) {
     const size_t lds = WPB * ld * sizeof(float);
     const int gx = rows_grid(N, 64);
     const long nwg = (long)B * gx;
@@ -510,11 +509,46 @@ extern "C" int cmpc_convlstm_bwd(int dt, const void* dh, const void* dc_new, con
         if (cmpc_reduce_parts_f32(part + (2 * q) * ld, 6 * ld, 1, (int)nwg, 1, ld, M, dln->dgamma[q], 0, 0, 1, ST)) return CMPC_EHIP;
         if (cmpc_reduce_parts_f32(part + (2 * q + 1) * ld, 6 * ld, 1, (int)nwg, 1, ld, M, dln->dbeta[q], 0, 0, 1, ST)) return CMPC_EHIP;
     }
-    CLSTM_NB(ld, CMPC_DISPATCH_DT(dt, {
-        hipLaunchKernelGGL((clstm_bwd3_kernel<T, NBX>), dim3(rows_grid(N, 200), B), dim3(256), 0, ST,
-                           (const T*)Yg, (const T*)c_prev, W_ci, W_cf, sums, bsums, (T*)dYg, (T*)dc_prev, dW_ci, dW_cf, B, N, ld, M);
-        hipLaunchKernelGGL((clstm_peephole_grad_kernel<T, NBX>), dim3(rows_grid(N, 512)), dim3(256), 0, ST,
-                           (const T*)dYg, (const T*)c_prev, (const T*)c_pre, dW_ci, dW_cf, dW_co, B, N, ld, M);
-    }));
+    CLSTM_NB(ld, CMPC_DISPATCH_DT(dt, hipLaunchKernelGGL((clstm_bwd3_kernel<T, NBX>), dim3(rows_grid(N, 200), B), dim3(256), 0, ST,
+                           (const T*)Yg, (const T*)c_prev, W_ci, W_cf, sums, bsums, (T*)dYg, (T*)dc_prev, nullptr, nullptr, B, N, ld, M)));
+    return CMPC_OK;
+}
+// the peephole rows' gradient: reads the finished dYg of passes 1-3 and adds into dW_c* (one writer per element, no atomics: the
+// launches of the time steps must stay ordered among themselves); nothing before the optimizer reads what it writes
+static int clstm_peephole(int dt, const void* dYg, const void* c_prev, const void* c_pre, float* dW_ci, float* dW_cf, float* dW_co,
+                           int B, int N, int ld, int M, void* stream) {
+    CLSTM_NB(ld, CMPC_DISPATCH_DT(dt, hipLaunchKernelGGL((clstm_peephole_grad_kernel<T, NBX>), dim3(rows_grid(N, 512)), dim3(256), 0, ST,
+                           (const T*)dYg, (const T*)c_prev, (const T*)c_pre, dW_ci, dW_cf, dW_co, B, N, ld, M)));
+    return CMPC_OK;
+}
+
+extern "C" int cmpc_convlstm_bwd(int dt, const void* dh, const void* dc_new, const void* Yg, const void* c_prev, const void* c_pre,
+                                 const float* W_ci, const float* W_cf, const float* W_co,
+                                 const cmpc_convlstm_ln* ln, const double* sums, void* dYg, void* dc_prev,
+                                 float* dW_ci, float* dW_cf, float* dW_co, const cmpc_convlstm_dln* dln, void* scr, double* bsums,
+                                 int B, int N, int ld, int M, void* stream) {
+    cmpc_op_scope op_("convlstm_bwd");
+    if (!ok("convlstm_bwd", dt, ld, M)) return CMPC_EINVAL;
+    if (int rc = clstm_bwd_gates(dt, dh, dc_new, Yg, c_prev, c_pre, W_ci, W_cf, W_co, ln, sums, dYg, dc_prev, dln, scr, bsums, B, N, ld, M, stream)) return rc;
+    if (int rc = clstm_peephole(dt, dYg, c_prev, c_pre, dW_ci, dW_cf, dW_co, B, N, ld, M, stream)) return rc;
     return cmpc_check_launch("convlstm_bwd");
+}
+
+// cmpc_convlstm_bwd in two calls, for a caller that keeps the peephole gradient off the recurrence's serial chain: _gates is passes 1-3
+// (dYg, dc_prev, the LayerNorm gradients), _peephole_grad the launch that adds into dW_ci / dW_cf / dW_co.  Same kernels, same grids.
+extern "C" int cmpc_convlstm_bwd_gates(int dt, const void* dh, const void* dc_new, const void* Yg, const void* c_prev, const void* c_pre,
+                                       const float* W_ci, const float* W_cf, const float* W_co,
+                                       const cmpc_convlstm_ln* ln, const double* sums, void* dYg, void* dc_prev,
+                                       const cmpc_convlstm_dln* dln, void* scr, double* bsums,
+                                       int B, int N, int ld, int M, void* stream) {
+    cmpc_op_scope op_("convlstm_bwd_gates");
+    if (!ok("convlstm_bwd_gates", dt, ld, M)) return CMPC_EINVAL;
+    if (int rc = clstm_bwd_gates(dt, dh, dc_new, Yg, c_prev, c_pre, W_ci, W_cf, W_co, ln, sums, dYg, dc_prev, dln, scr, bsums, B, N, ld, M, stream)) return rc;
+    return cmpc_check_launch("convlstm_bwd_gates");
+}
+extern "C" int cmpc_convlstm_peephole_grad(int dt, const void* dYg, const void* c_prev, const void* c_pre,
+                                           float* dW_ci, float* dW_cf, float* dW_co, int B, int N, int ld, int M, void* stream) {
+    if (!ok("convlstm_peephole_grad", dt, ld, M)) return CMPC_EINVAL;
+    if (int rc = clstm_peephole(dt, dYg, c_prev, c_pre, dW_ci, dW_cf, dW_co, B, N, ld, M, stream)) return rc;
+    return cmpc_check_launch("convlstm_peephole_grad");
 }

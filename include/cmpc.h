@@ -213,6 +213,17 @@ int cmpc_convlstm_bwd(int dt, const void* dh, const void* dc_new, const void* Yg
                       const cmpc_convlstm_ln* ln, const double* sums, void* dYg, void* dc_prev,
                       float* dW_ci, float* dW_cf, float* dW_co, const cmpc_convlstm_dln* dln, void* scr, double* bsums,
                       int B, int N, int ld, int M, void* stream);
+/* cmpc_convlstm_bwd in two calls (same kernels, grids and sums; the pair in this order on one stream IS cmpc_convlstm_bwd): _gates
+ * runs the three passes (dYg, dc_prev, LayerNorm gradients), _peephole_grad the last launch, which reads the finished dYg and adds
+ * into dW_ci / dW_cf (skipped when c_prev NULL) / dW_co.  A caller may issue the second anywhere behind the first; the peephole
+ * launches of several time steps add into the same rows without atomics and must stay ordered among themselves. */
+int cmpc_convlstm_bwd_gates(int dt, const void* dh, const void* dc_new, const void* Yg, const void* c_prev, const void* c_pre,
+                            const float* W_ci, const float* W_cf, const float* W_co,
+                            const cmpc_convlstm_ln* ln, const double* sums, void* dYg, void* dc_prev,
+                            const cmpc_convlstm_dln* dln, void* scr, double* bsums,
+                            int B, int N, int ld, int M, void* stream);
+int cmpc_convlstm_peephole_grad(int dt, const void* dYg, const void* c_prev, const void* c_pre,
+                                float* dW_ci, float* dW_cf, float* dW_co, int B, int N, int ld, int M, void* stream);
 
 /* ---- score heads, resize_bilinear, sigmoid, weighed_logistic_loss, mIoU
  *      (CMPC_model.py:128-142,440-447,486-490; util/loss.py:6-16) -------------------------- */

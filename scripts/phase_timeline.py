@@ -28,6 +28,15 @@ for i in range(1, len(steps) - 1):
     for name, t in steps[i]:
         acc.setdefault(name, []).append(t - t0)
     acc.setdefault("next fwd:start", []).append(steps[i + 1][0][1] - t0)
-print("phase boundary, ms after fwd:start on the GPU clock (mean over %d steps)" % (len(steps) - 2))
+print("phase boundary, ms after fwd:start on the GPU clock (min / mean / max over %d steps)" % (len(steps) - 2))
 for name, v in sorted(acc.items(), key=lambda kv: sum(kv[1]) / len(kv[1])):
-    print(f"  {name:22s} {sum(v)/len(v):8.3f}")
+    print(f"  {name:22s} {min(v):8.3f} {sum(v)/len(v):8.3f} {max(v):8.3f}")
+# the intervals between boundaries, per step (a boundary's spread above includes the drift of everything before it)
+IV = [("fwd:level_c3_done", "fwd:exch1_done"), ("fwd:exch1_done", "fwd:clstm_done"), ("bwd:start", "bwd:clstm_done"),
+      ("bwd:clstm_done", "bwd:exch2_done"), ("bwd:exch2_done", "bwd:exch1_done"), ("bwd:clstm_done", "bwd:exch1_done"),
+      ("bwd:text_done", "bwd:end"), ("bwd:text_done", "opt:end"), ("fwd:start", "next fwd:start")]
+print("interval, ms (min / mean / max)")
+for a, b in IV:
+    if a in acc and b in acc and len(acc[a]) == len(acc[b]):
+        d = [y - x for x, y in zip(acc[a], acc[b])]
+        print(f"  {a + ' -> ' + b:44s} {min(d):8.3f} {sum(d)/len(d):8.3f} {max(d):8.3f}")
