@@ -124,6 +124,16 @@ EVAL_MAX_BATCH = 32      # CMPC_EVAL_MAX_BATCH
 EVAL_F32, EVAL_U8 = 0, 1
 
 
+class TrainDesc(C.Structure):
+    """cmpc_train_desc"""
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int), ("w", C.c_int), ("c", C.c_int),
+                ("rh", C.c_int), ("rw", C.c_int), ("top", C.c_int), ("left", C.c_int),
+                ("kind", C.c_int), ("match", C.c_int), ("key", C.c_ubyte * 4)]
+
+
+ANN_COLOR, ANN_PLAIN = 0, 1
+
+
 class Fetches(C.Structure):
     """cmpc_fetches"""
     _fields_ = [("pred", C.c_void_p), ("up", C.c_void_p), ("sigm", C.c_void_p)]
@@ -236,6 +246,7 @@ SIGNATURES = {
     "cmpc_dense_crf_lattice": [_P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P],
     "cmpc_eval_prep": [_P, _L, C.POINTER(EvalDesc), _I, _I, _I, _P, _P, _P],
     "cmpc_eval_mask_iu": [_P, _I, _I, _I, _I, _F, _P, _L, C.POINTER(EvalDesc), _P, _P, _P],
+    "cmpc_train_prep": [_P, _L, C.POINTER(EvalDesc), _P, _L, C.POINTER(TrainDesc), _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "cmpc_launch_trace": [_I, _P],
     "cmpc_launch_trace_read": [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_L)],
     "cmpc_kernel_timing": [_P, _I],
@@ -250,7 +261,7 @@ _lib = None
 
 
 # op-level entry points younger than the oldest build still used as the `prev` side of an A/B run; nothing in the package calls them
-_AB_OPTIONAL = ("cmpc_convlstm_bwd_gates", "cmpc_convlstm_peephole_grad")
+_AB_OPTIONAL = ("cmpc_convlstm_bwd_gates", "cmpc_convlstm_peephole_grad", "cmpc_train_prep")
 
 
 def load():

@@ -2,6 +2,7 @@
 //
 //   eval_prep     proc_im = img_as_ubyte(resize_and_pad(im, H, W)); feed = proc_im[..., ::-1].astype(float32) - mu
 //   eval_mask_iu  I, U of resize_and_crop(up >= thresh, mh, mw) against the ground truth at its original size
+//   train_target  target_fine = resize_and_pad(mask_obj, H, W) > 0 of the training reader, and its foreground count (cmpc_train_prep)
 //
 // The resampler is skimage.transform.resize as cmpc-refseg_amd/hostutil.py restates it on scipy.ndimage: a mirror-mode Gaussian
 // (sigma = (f - 1) / 2, radius int(4 sigma + 0.5)) on every shrinking axis, then ndimage.zoom(order=1, mode="mirror", grid_mode=True).
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(NTHR) void eval_prep_kernel(PrepArgs a) {
                 if (C == 1) q[1] = q[2] = q[0];                              // build_batches.py:67-68
             }
             const int64_t o = (((int64_t)b * a.H + oy) * a.W + ox) * 3;
-            a.proc[o] = q[0]; a.proc[o + 1] = q[1]; a.proc[o + 2] = q[2];
+            if (a.proc) { a.proc[o] = q[0]; a.proc[o + 1] = q[1]; a.proc[o + 2] = q[2]; }
             // proc_im[..., ::-1].astype(float32) -= mu: a float64 subtract rounded once to float32
             a.feed[o] = (float)((double)q[2] - mu[0]);
             a.feed[o + 1] = (float)((double)q[1] - mu[1]);
@@ -319,6 +320,211 @@ size_t prep_lds(const cmpc_eval_desc* ds, const SampleGeo* geo, int B, int ty, i
     return m;
 }
 
+// ---- train_target: target_fine = resize_and_pad(mask_obj, H, W) > 0 of the training reader (data_reader_refvos.py:30,33,42) ----------
+// As in eval_mask_iu the resampled value is positive exactly when the object bit is set under a tap with non-zero weight, each tap
+// widened by the Gaussian window.  Mirrored window indices land inside the clipped window [c - r, c + r] ∩ [0, n), so the window OR is
+// the OR over the clipped rectangle, and that is separable: a workgroup stages the object bits of its tile's source footprint plus
+// halo (0 outside the image) as bytes, four pixels per 32-bit word, ORs rows (word-wide, funnel shifts), then columns, and every
+// thread reads its <= 4 taps from the dilated map.
+struct TrainArgs {
+    const unsigned char* ann; int64_t ann_bytes;
+    float* target; unsigned long long* pos;
+    int H, W, B, order, ty, tx;
+    cmpc_train_desc d[CMPC_EVAL_MAX_BATCH];
+    SampleGeo g[CMPC_EVAL_MAX_BATCH];
+};
+
+// LDS words of one tile: bits [NYr][wr] (staged, halo included), hb [NYr][wn] (row OR), dil [NYb][wn] (row and column OR)
+struct TileLds { int NYb, NYr, wn, wr; };
+__host__ __device__ inline TileLds tile_lds(const SampleGeo& g, int ty, int tx, int h, int w) {
+    TileLds t; int NXb, NXr;
+    tile_extent(g.zy, ty, g.ry, h, t.NYb, t.NYr);
+    tile_extent(g.zx, tx, g.rx, w, NXb, NXr);
+    t.wn = (NXb + 3) / 4;
+    t.wr = t.wn + (2 * g.rx) / 4 + 2;            // the row pass reads words g .. g + 2 rx / 4 + 1
+    return t;
+}
+__host__ __device__ inline size_t tile_lds_bytes(const TileLds& t) { return sizeof(uint32_t) * ((size_t)t.NYr * t.wr + (size_t)t.NYr * t.wn + (size_t)t.NYb * t.wn); }
+
+__device__ __forceinline__ uint32_t ld_word(const unsigned char* base, int64_t k, int64_t nbytes) {
+    if ((k + 1) * 4 <= nbytes) return ((const uint32_t*)base)[k];
+    uint32_t v = 0;
+    for (int j = 0; j < 4; ++j) if (k * 4 + j < nbytes) v |= (uint32_t)base[k * 4 + j] << (8 * j);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t funnel(uint32_t hi, uint32_t lo, int bytes) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * bytes)); }
+
+// object bits (one byte each, 0 / 1) of the 4 pixels whose first byte is at A: C + 1 aligned 32-bit loads, then compile-time byte picks
+template <int C>
+__device__ __forceinline__ uint32_t object_bits4(const unsigned char* ann, int64_t nbytes, int64_t A, int kind, int match, uint32_t key) {
+    const int64_t k0 = A >> 2;
+    const int sh = (int)(A & 3);
+    uint32_t wd[C + 1], al[C];
+    for (int i = 0; i <= C; ++i) wd[i] = (i < C || sh) ? ld_word(ann, k0 + i, nbytes) : 0u;
+    for (int i = 0; i < C; ++i) al[i] = funnel(wd[i + 1], wd[i], sh);
+    uint32_t out = 0;
+    for (int j = 0; j < 4; ++j) {
+        bool f;
+        if (C == 1) {
+            const uint32_t v = (al[0] >> (8 * j)) & 255u;
+            f = kind == CMPC_ANN_PLAIN ? v != 0 : v == (key & 255u);
+        } else {
+            f = true;
+            for (int ch = 0; ch < 3; ++ch) {
+                const int p = j * C + ch;
+                const uint32_t v = (al[p >> 2] >> (8 * (p & 3))) & 255u;
+                f = f && (ch >= match || v == ((key >> (8 * ch)) & 255u));
+            }
+        }
+        out |= (uint32_t)f << (8 * j);
+    }
+    return out;
+}
+
+__device__ __forceinline__ bool object_bit(const unsigned char* p, int C, int kind, int match, uint32_t key) {
+    if (kind == CMPC_ANN_PLAIN) return p[0] != 0;
+    bool f = true;
+    for (int ch = 0; ch < 3 && ch < C; ++ch) f = f && (ch >= match || p[ch] == ((key >> (8 * ch)) & 255u));
+    return f;
+}
+
+__global__ __launch_bounds__(NTHR) void train_target_kernel(TrainArgs a) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int b = blockIdx.z;
+    const cmpc_train_desc d = a.d[b];
+    const SampleGeo g = a.g[b];
+    const int C = d.c, h = d.h, w = d.w;
+    const uint32_t key = (uint32_t)d.key[0] | (uint32_t)d.key[1] << 8 | (uint32_t)d.key[2] << 16;
+    const TileLds L = tile_lds(g, a.ty, a.tx, h, w);
+    uint32_t* bits = (uint32_t*)lds;                    // [NYr][wr]
+    uint32_t* hb = bits + L.NYr * L.wr;                  // [NYr][wn]
+    uint32_t* dil = hb + L.NYr * L.wn;                   // [NYb][wn]
+    const unsigned char* dilb = (const unsigned char*)dil;
+    const unsigned char* src = a.ann + d.offset;
+    unsigned long long cnt = 0;
+
+    {                                                   // one output tile per workgroup
+        const int oy0 = blockIdx.y * a.ty, ox0 = blockIdx.x * a.tx;
+        const int ya = max(oy0 - d.top, 0), yb = min(oy0 + a.ty - d.top, d.rh);
+        const int xa = max(ox0 - d.left, 0), xb = min(ox0 + a.tx - d.left, d.rw);
+        const bool any = ya < yb && xa < xb;
+        int lo_y = 0, lo_x = 0, ny = 0, nx = 0;
+        if (any) {
+            // source rows / columns the taps can reach (eval_prep's footprint; the order-0 tap floor(cc + 0.5) lies inside it)
+            lo_y = max(0, (int)floor(((double)ya + 0.5) * g.zy - 0.5) - 1);
+            lo_x = max(0, (int)floor(((double)xa + 0.5) * g.zx - 0.5) - 1);
+            ny = min(h - 1, (int)floor(((double)(yb - 1) + 0.5) * g.zy - 0.5) + 2) - lo_y + 1;
+            nx = min(w - 1, (int)floor(((double)(xb - 1) + 0.5) * g.zx - 0.5) + 2) - lo_x + 1;
+            ny = min(ny, L.NYb); nx = min(nx, 4 * L.wn);    // never binding (tile_extent has slack): keeps LDS indexing in range
+            const int nyr = ny + 2 * g.ry, wn = (nx + 3) / 4;
+            const int Y0 = lo_y - g.ry, X0 = lo_x - g.rx;
+            // stage: one compare per source pixel, four pixels per thread and store
+            for (int i = threadIdx.x; i < nyr * L.wr; i += NTHR) {
+                const int r = i / L.wr, q = i - r * L.wr;
+                const int sy = Y0 + r, sx = X0 + 4 * q;
+                uint32_t v = 0;
+                if (sy >= 0 && sy < h && sx + 3 >= 0 && sx < w) {
+                    if (sx >= 0 && sx + 3 < w) {
+                        const int64_t A = d.offset + ((int64_t)sy * w + sx) * C;
+                        v = C == 1 ? object_bits4<1>(a.ann, a.ann_bytes, A, d.kind, d.match, key)
+                          : C == 3 ? object_bits4<3>(a.ann, a.ann_bytes, A, d.kind, d.match, key)
+                                   : object_bits4<4>(a.ann, a.ann_bytes, A, d.kind, d.match, key);
+                    } else {
+                        for (int j = 0; j < 4; ++j)
+                            if (sx + j >= 0 && sx + j < w)
+                                v |= (uint32_t)object_bit(src + ((int64_t)sy * w + sx + j) * C, C, d.kind, d.match, key) << (8 * j);
+                    }
+                }
+                bits[i] = v;
+            }
+            __syncthreads();
+            // rows: hb[r][x] = OR bits[r][x .. x + 2 rx]
+            for (int i = threadIdx.x; i < nyr * wn; i += NTHR) {
+                const int r = i / wn, q = i - r * wn;
+                const uint32_t* row = bits + r * L.wr + q;
+                uint32_t lo = row[0], acc = lo;
+                for (int k = 0; 4 * k < 2 * g.rx; ++k) {
+                    const uint32_t hi = row[k + 1];
+                    for (int s = 1; s <= 4; ++s)
+                        if (4 * k + s <= 2 * g.rx) acc |= funnel(hi, lo, s);
+                    lo = hi;
+                }
+                hb[r * L.wn + q] = acc;
+            }
+            __syncthreads();
+            // columns: dil[y][x] = OR hb[y .. y + 2 ry][x]
+            for (int i = threadIdx.x; i < ny * wn; i += NTHR) {
+                const int y = i / wn, q = i - y * wn;
+                uint32_t acc = 0;
+                for (int s = 0; s <= 2 * g.ry; ++s) acc |= hb[(y + s) * L.wn + q];
+                dil[y * L.wn + q] = acc;
+            }
+            __syncthreads();
+        }
+        const int ly = threadIdx.x / a.tx, lx = threadIdx.x - ly * a.tx;
+        const int oy = oy0 + ly, ox = ox0 + lx;
+        if (ly < a.ty && oy < a.H && ox < a.W) {
+            const int y = oy - d.top, x = ox - d.left;
+            bool f = false;
+            if (any && y >= 0 && y < d.rh && x >= 0 && x < d.rw) {
+                int ys[2], xs[2], nty = 1, ntx = 1;
+                if (a.order == 0) {
+                    // ndimage.zoom order 0: the sample nearest the grid-mode coordinate
+                    ys[0] = min(max((int)floor((((double)y + 0.5) * g.zy - 0.5) + 0.5), 0), h - 1);
+                    xs[0] = min(max((int)floor((((double)x + 0.5) * g.zx - 0.5) + 0.5), 0), w - 1);
+                } else {
+                    double wy0, wy1, wx0, wx1;
+                    zoom_taps(y, g.zy, h, ys[0], ys[1], wy0, wy1);
+                    zoom_taps(x, g.zx, w, xs[0], xs[1], wx0, wx1);
+                    nty = wy1 != 0.0 ? 2 : 1; ntx = wx1 != 0.0 ? 2 : 1;            // w0 = 1 - t is never 0
+                }
+                for (int iy = 0; iy < nty; ++iy)
+                    for (int ix = 0; ix < ntx; ++ix) {
+                        const int ry_ = ys[iy] - lo_y, rx_ = xs[ix] - lo_x;
+                        if (ry_ >= 0 && ry_ < ny && rx_ >= 0 && rx_ < nx) f = f || dilb[(ry_ * L.wn) * 4 + rx_] != 0;
+                    }
+            }
+            a.target[((int64_t)b * a.H + oy) * a.W + ox] = f ? 1.0f : 0.0f;
+            cnt += f;
+        }
+    }
+    // wave sums, then one integer atomic per workgroup
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+    __shared__ unsigned long long sC[NTHR / 64];
+    if ((threadIdx.x & 63) == 0) sC[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+        for (int i = 0; i < NTHR / 64; ++i) t += sC[i];
+        if (t) atomicAdd(&a.pos[b], t);
+    }
+}
+
+// validated descriptors -> one eval_prep_kernel launch (proc_im may be NULL: cmpc_train_prep)
+int launch_prep(const char* who, const unsigned char* src, int64_t src_bytes, const cmpc_eval_desc* descs_host, int B, int H, int W,
+                unsigned char* proc_im, float* feed, hipStream_t stream) {
+    PrepArgs a;
+    const int rc = check_descs(who, descs_host, B, src_bytes, H, W, true, a.g);
+    if (rc) return rc;
+    // tile: 256 threads as ty x tx output pixels; shrink the tile until the staged footprint fits in 64 KB of LDS
+    static const int shapes[][2] = {{8, 32}, {4, 32}, {2, 32}, {1, 32}, {1, 16}, {1, 8}, {1, 4}, {1, 1}};
+    size_t lds = 0; int ty = 0, tx = 0;
+    for (auto& s : shapes) {
+        lds = prep_lds(descs_host, a.g, B, s[0], s[1]);
+        if (lds <= LDS_CAP) { ty = s[0]; tx = s[1]; break; }
+    }
+    if (!ty) { cmpc_set_error("%s: source footprint does not fit in LDS", who); return CMPC_EINVAL; }
+    a.src = src; a.src_bytes = src_bytes; a.proc = proc_im; a.feed = feed;
+    a.H = H; a.W = W; a.B = B; a.ty = ty; a.tx = tx;
+    a.tiles_x = (W + tx - 1) / tx;
+    a.tiles = a.tiles_x * ((H + ty - 1) / ty);
+    for (int b = 0; b < B; ++b) a.d[b] = descs_host[b];
+    const int per_sample = std::max(1, std::min(a.tiles, 2048 / B));        // memory-bound cap: ~2048 workgroups per launch
+    hipLaunchKernelGGL(eval_prep_kernel, dim3(per_sample, B), dim3(NTHR), lds, stream, a);
+    return cmpc_check_launch(who);
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -328,25 +534,7 @@ extern "C" int cmpc_eval_prep(const unsigned char* src, int64_t src_bytes, const
     if (!src || !descs_host || !proc_im || !feed) { cmpc_set_error("eval_prep: NULL pointer"); return CMPC_EINVAL; }
     if (B <= 0 || B > CMPC_EVAL_MAX_BATCH) { cmpc_set_error("eval_prep: B = %d outside 1..%d", B, CMPC_EVAL_MAX_BATCH); return CMPC_EINVAL; }
     if (H <= 0 || W <= 0 || src_bytes <= 0) { cmpc_set_error("eval_prep: bad output size %d x %d or buffer length", H, W); return CMPC_EINVAL; }
-    PrepArgs a;
-    const int rc = check_descs("eval_prep", descs_host, B, src_bytes, H, W, true, a.g);
-    if (rc) return rc;
-    // tile: 256 threads as ty x tx output pixels; shrink the tile until the staged footprint fits in 64 KB of LDS
-    static const int shapes[][2] = {{8, 32}, {4, 32}, {2, 32}, {1, 32}, {1, 16}, {1, 8}, {1, 4}, {1, 1}};
-    size_t lds = 0; int ty = 0, tx = 0;
-    for (auto& s : shapes) {
-        lds = prep_lds(descs_host, a.g, B, s[0], s[1]);
-        if (lds <= LDS_CAP) { ty = s[0]; tx = s[1]; break; }
-    }
-    if (!ty) { cmpc_set_error("eval_prep: source footprint does not fit in LDS"); return CMPC_EINVAL; }
-    a.src = src; a.src_bytes = src_bytes; a.proc = proc_im; a.feed = feed;
-    a.H = H; a.W = W; a.B = B; a.ty = ty; a.tx = tx;
-    a.tiles_x = (W + tx - 1) / tx;
-    a.tiles = a.tiles_x * ((H + ty - 1) / ty);
-    for (int b = 0; b < B; ++b) a.d[b] = descs_host[b];
-    const int per_sample = std::max(1, std::min(a.tiles, 2048 / B));        // memory-bound cap: ~2048 workgroups per launch
-    hipLaunchKernelGGL(eval_prep_kernel, dim3(per_sample, B), dim3(NTHR), lds, ST, a);
-    return cmpc_check_launch("eval_prep");
+    return launch_prep("eval_prep", src, src_bytes, descs_host, B, H, W, proc_im, feed, ST);
 }
 
 extern "C" int cmpc_eval_mask_iu(const void* map, int map_dt, int B, int H, int W, float thresh, const unsigned char* gt, int64_t gt_bytes,
@@ -367,4 +555,58 @@ extern "C" int cmpc_eval_mask_iu(const void* map, int map_dt, int B, int H, int 
     if (map_dt == CMPC_EVAL_F32) hipLaunchKernelGGL(eval_mask_iu_kernel<float>, dim3(per_sample, B), dim3(NTHR), 0, ST, a);
     else hipLaunchKernelGGL(eval_mask_iu_kernel<unsigned char>, dim3(per_sample, B), dim3(NTHR), 0, ST, a);
     return cmpc_check_launch("eval_mask_iu");
+}
+
+extern "C" int cmpc_train_prep(const unsigned char* img, int64_t img_bytes, const cmpc_eval_desc* img_descs_host, const unsigned char* ann,
+                               int64_t ann_bytes, const cmpc_train_desc* ann_descs_host, int B, int H, int W, int order,
+                               unsigned char* proc_im, float* feed, float* target_fine, uint64_t* pos, void* stream) {
+    if (!ann || !ann_descs_host || !target_fine || !pos) { cmpc_set_error("train_prep: NULL pointer"); return CMPC_EINVAL; }
+    const bool images = img || img_descs_host || feed || proc_im;
+    if (images && (!img || !img_descs_host || !feed)) { cmpc_set_error("train_prep: NULL pointer (img, img_descs and feed go together)"); return CMPC_EINVAL; }
+    if (B <= 0 || B > CMPC_EVAL_MAX_BATCH) { cmpc_set_error("train_prep: B = %d outside 1..%d", B, CMPC_EVAL_MAX_BATCH); return CMPC_EINVAL; }
+    if (H <= 0 || W <= 0 || ann_bytes <= 0 || (images && img_bytes <= 0)) { cmpc_set_error("train_prep: bad output size %d x %d or buffer length", H, W); return CMPC_EINVAL; }
+    if (order != 0 && order != 1) { cmpc_set_error("train_prep: order %d is neither 0 nor 1", order); return CMPC_EINVAL; }
+    if ((uintptr_t)ann & 3) { cmpc_set_error("train_prep: the annotation buffer is not 4-byte aligned"); return CMPC_EINVAL; }
+    TrainArgs a;
+    cmpc_eval_desc e[CMPC_EVAL_MAX_BATCH];
+    for (int b = 0; b < B; ++b) {
+        const cmpc_train_desc& d = ann_descs_host[b];
+        if (d.kind != CMPC_ANN_COLOR && d.kind != CMPC_ANN_PLAIN) { cmpc_set_error("train_prep: sample %d: unknown annotation kind %d", b, d.kind); return CMPC_EINVAL; }
+        if (d.kind == CMPC_ANN_COLOR ? (d.c != 3 && d.c != 4) : d.c != 1) {
+            cmpc_set_error("train_prep: sample %d: %d channels for a %s annotation", b, d.c, d.kind == CMPC_ANN_COLOR ? "colour-coded" : "plain");
+            return CMPC_EINVAL;
+        }
+        if (d.kind == CMPC_ANN_COLOR ? (d.match < 1 || d.match > 3) : d.match != 0) {
+            cmpc_set_error("train_prep: sample %d: %d channels to match (1..3 for a colour-coded annotation, 0 for a plain mask)", b, d.match);
+            return CMPC_EINVAL;
+        }
+        e[b] = cmpc_eval_desc{d.offset, d.h, d.w, 1, d.rh, d.rw, d.top, d.left, 0};
+        if (d.h > 0 && d.w > 0 && d.offset >= 0 && d.offset <= ann_bytes && (int64_t)d.h * d.w * d.c > ann_bytes - d.offset) {
+            cmpc_set_error("train_prep: sample %d: offset %lld + %lld bytes beyond the buffer (%lld)", b, (long long)d.offset,
+                           (long long)d.h * d.w * d.c, (long long)ann_bytes);
+            return CMPC_EINVAL;
+        }
+    }
+    int rc = check_descs("train_prep", e, B, ann_bytes, H, W, true, a.g);
+    if (rc) return rc;
+    if (order == 0)
+        for (int b = 0; b < B; ++b) { a.g[b].sy = a.g[b].sx = 0.0; a.g[b].ry = a.g[b].rx = 0; }       // nearest sample: no Gaussian
+    static const int shapes[][2] = {{8, 32}, {4, 32}, {2, 32}, {1, 32}, {1, 16}, {1, 8}, {1, 4}, {1, 1}};
+    size_t lds = 0; int ty = 0, tx = 0;
+    for (auto& s : shapes) {
+        lds = 0;
+        for (int b = 0; b < B; ++b) lds = std::max(lds, tile_lds_bytes(tile_lds(a.g[b], s[0], s[1], ann_descs_host[b].h, ann_descs_host[b].w)));
+        if (lds <= LDS_CAP) { ty = s[0]; tx = s[1]; break; }
+    }
+    if (!ty) { cmpc_set_error("train_prep: source footprint does not fit in LDS"); return CMPC_EINVAL; }
+    if (images) {
+        rc = launch_prep("train_prep", img, img_bytes, img_descs_host, B, H, W, proc_im, feed, ST);
+        if (rc) return rc;
+    }
+    a.ann = ann; a.ann_bytes = ann_bytes; a.target = target_fine; a.pos = (unsigned long long*)pos;
+    a.H = H; a.W = W; a.B = B; a.order = order; a.ty = ty; a.tx = tx;
+    for (int b = 0; b < B; ++b) a.d[b] = ann_descs_host[b];
+    if (hipMemsetAsync(pos, 0, sizeof(uint64_t) * B, ST) != hipSuccess) { cmpc_set_error("train_prep: hipMemsetAsync"); return CMPC_EHIP; }
+    hipLaunchKernelGGL(train_target_kernel, dim3((W + tx - 1) / tx, (H + ty - 1) / ty, B), dim3(NTHR), lds, ST, a);
+    return cmpc_check_launch("train_prep");
 }

@@ -12,6 +12,9 @@ Resizing (util/im_processing.py:7-41) goes through scikit-image in the reference
 functions compute (pinned by hand-worked cases); `resize_and_pad` / `resize_and_crop` fill it with a restatement of
 `skimage.transform.resize` as scikit-image >= 0.19 documents it (order 1, mode "reflect", anti-aliasing Gaussian when shrinking,
 uint8 scaled to [0, 1]) on scipy.ndimage -- the resampled pixel values are PARITY-UNPINNED (no scikit-image to compare with).
+`skimage_like_resize` resamples a bool image like a float one (order 1); `resize_and_pad_order0` is the order-0 rule scikit-image >= 0.19
+documents for bool input, equally parity-unpinned.  `train_sample` is the training reader's per-sample work on both
+(util/data_reader_refvos.py:27-46).
 """
 from __future__ import annotations
 
@@ -193,3 +196,60 @@ def first_valid_idx(text_front_padded, pad: int = 0) -> int:
         raise ValueError("first_valid_idx: expected integer ids [T], got %s %s" % (a.dtype, a.shape))
     nz = np.flatnonzero(a != pad)
     return int(nz[0]) if nz.size else 0
+
+
+# ---- the training reader's per-sample work (util/data_reader_refvos.py:27-46, build_batches.py:62-75) -----------------------------------
+def object_mask(annotation, key=None, match: int = 1) -> np.ndarray:
+    """The object of one annotation as bool [h, w].  key given: a colour-coded annotation uint8 [h, w, 3|4] (alpha ignored,
+    data_reader_refvos.py:64); the object is where the first `match` channels equal the key's.  match=1 is the reference's rule,
+    `(mask == mask_color)[:, :, 0]` (data_reader_refvos.py:30): channel 0 alone decides; match=3 asks for all of R, G, B.
+    key None: a plain mask [h, w] (or [h, w, 1]) of any dtype, non-zero = object."""
+    a = np.asarray(annotation)
+    if key is None:
+        if a.ndim == 3 and a.shape[2] == 1:
+            a = a[:, :, 0]
+        if a.ndim != 2 or a.shape[0] == 0 or a.shape[1] == 0:
+            raise ValueError("plain mask: expected [h, w] with h, w > 0, got %s" % (a.shape,))
+        return a != 0
+    k = np.asarray(key).reshape(-1)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4) or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError("colour-coded annotation: expected uint8 [h, w, 3|4] with h, w > 0, got %s %s" % (a.dtype, a.shape))
+    if k.size < 3 or match not in (1, 2, 3) or np.any(k[:3] < 0) or np.any(k[:3] > 255):
+        raise ValueError("key colour must hold R, G, B in 0..255 and match must be 1, 2 or 3, got %s, %s" % (key, match))
+    return np.all(a[:, :, :match] == k[:match].astype(np.uint8), axis=2)
+
+
+def resize_and_pad_order0(mask: np.ndarray, input_h: int, input_w: int) -> np.ndarray:
+    """resize_and_pad of a BOOL image as scikit-image >= 0.19 documents resize for that dtype: order 0, no anti-aliasing, i.e. the source
+    sample nearest each pixel-area grid coordinate (ndimage.zoom order 0, mode "mirror", grid_mode).  skimage_like_resize above keeps
+    resampling a bool like a float (order 1); both are parity-unpinned against scikit-image itself (module header)."""
+    from scipy import ndimage as ndi
+    m = np.asarray(mask, dtype=bool)
+    h, w = m.shape
+    rh, rw, top, left = resize_and_pad_geometry(h, w, input_h, input_w)
+    r = m if (h, w) == (rh, rw) else ndi.zoom(m.astype(np.uint8), (rh / h, rw / w), order=0, mode="mirror", grid_mode=True) != 0
+    if r.shape != (rh, rw):
+        raise ValueError("resize_and_pad_order0: zoom gave %s for (%d, %d)" % (r.shape, rh, rw))
+    out = np.zeros((input_h, input_w), dtype=bool)
+    out[top: top + rh, left: left + rw] = r
+    return out
+
+
+def train_sample(image, annotation, key, H: int, W: int, order: int = 1, match: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """preprocess_data's two tensors for one raw sample (data_reader_refvos.py:27-46) as the train step is fed with them
+    (trainval_model.py:90-91): im float32 [H, W, 3] = img_as_ubyte(resize_and_pad(image))[..., ::-1] - mu (a grey image tiled to three
+    channels, build_batches.py:67-68) and target_fine float32 [H, W, 1] in {0, 1} = resize_and_pad(mask_obj) > 0.  order 1 resamples the
+    object mask like a float image (resize_and_pad above), order 0 as a bool image (resize_and_pad_order0)."""
+    if order not in (0, 1):
+        raise ValueError("order must be 0 or 1, got %r" % (order,))
+    im = np.asarray(image)
+    if im.dtype != np.uint8:
+        raise ValueError("image: expected uint8, got %s" % im.dtype)
+    proc = img_as_ubyte(resize_and_pad(im, H, W))
+    if proc.ndim == 2 or proc.shape[2] == 1:
+        proc = np.repeat(proc.reshape(H, W, 1), 3, 2)
+    feed = proc[..., ::-1].astype(np.float32)
+    feed -= MU
+    obj = object_mask(annotation, key, match)
+    tgt = resize_and_pad(obj, H, W) > 0 if order == 1 else resize_and_pad_order0(obj, H, W)
+    return feed, tgt.astype(np.float32)[..., None]

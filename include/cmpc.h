@@ -561,6 +561,29 @@ int cmpc_eval_prep(const unsigned char* src, int64_t src_bytes, const cmpc_eval_
 int cmpc_eval_mask_iu(const void* map, int map_dt, int B, int H, int W, float thresh, const unsigned char* gt, int64_t gt_bytes,
                       const cmpc_eval_desc* descs_host, uint64_t* iu, unsigned char* mask_out, void* stream);
 
+/* ---- Training feed from raw samples (util/data_reader_refvos.py:27-46, build_batches.py:62-75): the image half is cmpc_eval_prep's
+ *      kernel, the mask half cuts the object out of the annotation and resamples it.  One annotation descriptor per sample (HOST memory,
+ *      validated before anything is launched, passed by value); B <= CMPC_EVAL_MAX_BATCH --------------------------------------------- */
+#define CMPC_ANN_COLOR 0             /* colour-coded [h, w, 3|4] uint8: object = the first `match` channels equal `key` */
+#define CMPC_ANN_PLAIN 1             /* plain mask [h, w] uint8: object = non-zero */
+typedef struct {
+    int64_t offset;                  /* byte offset of the annotation in the packed uint8 buffer ([h, w, c] row-major) */
+    int h, w, c;                     /* c: 3 or 4 (alpha ignored) for CMPC_ANN_COLOR, 1 for CMPC_ANN_PLAIN */
+    int rh, rw, top, left;           /* resize_and_pad_geometry(h, w, H, W) */
+    int kind;                        /* CMPC_ANN_COLOR / CMPC_ANN_PLAIN */
+    int match;                       /* CMPC_ANN_COLOR: leading channels compared, 1 (the reference: (mask == color)[:, :, 0]) .. 3; else 0 */
+    unsigned char key[4];            /* the object's colour (R, G, B, unused) */
+} cmpc_train_desc;
+/* target_fine [B, H, W, 1] float32 in {0, 1} = resize_and_pad(mask_obj, H, W) > 0 with 0 in the padding, and pos [B] uint64 = the number
+ * of foreground pixels of each target (exact integers).  order 1: hostutil.resize_and_pad's resampler (mirror Gaussian when shrinking,
+ * bilinear zoom) -- the OR of the object bit over the taps with non-zero weight; order 0: nearest source pixel, no Gaussian
+ * (ndimage.zoom(order=0, mode="mirror", grid_mode=True)).  ann: packed uint8 annotations, 4-byte aligned, ann_bytes long.
+ * img / img_descs / feed: the images of the same samples, prepared exactly as cmpc_eval_prep prepares them (proc_im may be NULL);
+ * all three NULL = targets only. */
+int cmpc_train_prep(const unsigned char* img, int64_t img_bytes, const cmpc_eval_desc* img_descs_host, const unsigned char* ann,
+                    int64_t ann_bytes, const cmpc_train_desc* ann_descs_host, int B, int H, int W, int order, unsigned char* proc_im,
+                    float* feed, float* target_fine, uint64_t* pos, void* stream);
+
 /* Host utility (no GPU): CRC-32C of `n` bytes, continuing from `crc` (0 to start) -- the checksum of TensorFlow's tensor-bundle
  * checkpoints (trainval_model.py:46-63 restores / saves them; cmpc-refseg_amd/tf_bundle.py reads and writes the format). */
 uint32_t cmpc_crc32c(uint32_t crc, const void* data, size_t n);
