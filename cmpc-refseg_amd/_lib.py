@@ -122,6 +122,8 @@ class EvalDesc(C.Structure):
 
 EVAL_MAX_BATCH = 32      # CMPC_EVAL_MAX_BATCH
 EVAL_F32, EVAL_U8 = 0, 1
+GV_NORM_BATCH, GV_NORM_SAMPLE = 0, 1      # CMPC_GV_NORM_*
+GV_NORMS = {"batch": GV_NORM_BATCH, "sample": GV_NORM_SAMPLE}
 
 
 class TrainDesc(C.Structure):
@@ -242,10 +244,12 @@ SIGNATURES = {
     "cmpc_phase_marks": [_P, _I],
     "cmpc_phase_marks_read": [_P, _I, C.POINTER(C.c_char_p), C.POINTER(C.c_float)],
     "cmpc_set_lanes": [_P, _I],
+    "cmpc_set_gv_norm": [_P, _I],
     "cmpc_dense_crf": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P],
     "cmpc_dense_crf_lattice": [_P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P],
     "cmpc_eval_prep": [_P, _L, C.POINTER(EvalDesc), _I, _I, _I, _P, _P, _P],
     "cmpc_eval_mask_iu": [_P, _I, _I, _I, _I, _F, _P, _L, C.POINTER(EvalDesc), _P, _P, _P],
+    "cmpc_eval_mask_out": [_P, _I, _I, _I, _I, _F, C.POINTER(EvalDesc), _P, _L, _I, _P],
     "cmpc_train_prep": [_P, _L, C.POINTER(EvalDesc), _P, _L, C.POINTER(TrainDesc), _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "cmpc_launch_trace": [_I, _P],
     "cmpc_launch_trace_read": [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_L)],

@@ -316,6 +316,10 @@ struct cmpc_engine_s {
     bool have_target = false;
     bool bwd_zeroed = false;      // the backward pass's accumulate-into buffers and the gradient buffer were cleared by the last cmpc_forward
     bool grads_pending = false;   // a cmpc_backward wrote gradients that no optimizer step (its last bucket) has consumed yet
+    // l2_normalize of gv_lang (CMPC_model.py:241): over the whole [B, M] tensor, as the graph at batch_size = B computes it, or per sample,
+    // as the same line computes at batch_size = 1.  gv_norm is what cmpc_set_gv_norm asked for; cmpc_forward latches it into gv_norm_fwd,
+    // which both passes of that step read, so that cmpc_backward differentiates the function its forward computed
+    int gv_norm = CMPC_GV_NORM_BATCH, gv_norm_fwd = CMPC_GV_NORM_BATCH;
     const int32_t* seq_len_feed = nullptr; const float* target_feed = nullptr;      // caller-owned feeds the backward pass re-reads
     hipStream_t last_main = nullptr; long l0 = 0;
     // Gradient buckets: contiguous ranges of the flat gradient buffer in the order they become final during cmpc_backward
@@ -802,7 +806,7 @@ void plan_workspace(E* e, Bump& zf, Bump& zb, Bump& g) {
         X.q = (float*)g.take((size_t)B * Mp * F); X.kq = (float*)g.take((size_t)B * Mp * F);
         X.logits = (float*)g.take((size_t)B * N * F); X.attn = (float*)g.take((size_t)B * N * F);
         X.pooled = (float*)zf.take((size_t)B * Mp * F);
-        X.gvpre = (float*)g.take((size_t)B * Mp * F); X.gv = (float*)g.take((size_t)B * Mp * F); X.rs1 = (float*)g.take(256);
+        X.gvpre = (float*)g.take((size_t)B * Mp * F); X.gv = (float*)g.take((size_t)B * Mp * F); X.rs1 = (float*)g.take(std::max<size_t>(256, (size_t)B * F));     // one rstd, or one per sample
         for (int k = 0; k < 2; ++k) { X.g[k] = (float*)g.take((size_t)B * Mp * F); X.r[k] = g.take((size_t)R * Mp * es); }
         X.out = g.take((size_t)R * Mp * es); X.rstd = (float*)g.take((size_t)R * F);
         X.dfeat = g.take((size_t)R * Mp * es);
@@ -1739,7 +1743,8 @@ int exchange_attn_fwd(E* e, hipStream_t st, int xi, const void* feat, int nbr) {
     const int ldk = Mp + Cp; const std::string gvk = fmt("gv_%s.t", lv);
     GemmOpt g; g.n_valid = M; g.bias = pptr(e, fmt("gv_lang_%sgv_f1/biases", lv)); if (e->gv_tanh) g.act = ACT_TANH;
     CK(gemm_nt(st, DT_F32, {{X.pooled, Mp, opp(e, gvk), ldk, Mp}, {e->nec, Cp, opp(e, gvk, 0, Mp), ldk, Cp}}, X.gvpre, Mp, B, Mp, g));
-    CK(cmpc_l2norm_all_fwd(X.gvpre, X.gv, X.rs1, B * Mp, st));
+    if (e->gv_norm_fwd == CMPC_GV_NORM_SAMPLE) CK(cmpc_l2norm_rows_fwd(DT_F32, X.gvpre, X.gv, X.rs1, nullptr, B, Mp, M, st));
+    else CK(cmpc_l2norm_all_fwd(X.gvpre, X.gv, X.rs1, B * Mp, st));
     const char* fn[2] = {"f1", "f2"};
     for (int i = 0; i < nbr; ++i) {
         GemmOpt a; a.n_valid = M; a.bias = pptr(e, fmt("lang_feat_%s_%s/biases", lv, fn[i])); a.act = ACT_SIGMOID;
@@ -1822,7 +1827,8 @@ int exchange_feat_bwd(E* e, hipStream_t st, int xi, const void* feat, int nbr) {
         GemmOpt a; a.n_valid = M; a.accumulate = i == 1;
         CK(gemm_nt(st, DT_F32, {{X.dg[i], Mp, opp(e, fmt("lfeat_%s_%s.n", lv, fn[i])), Mp, Mp}}, X.dgv, Mp, B, Mp, a));
     }
-    CK(cmpc_l2norm_all_bwd(X.dgv, X.gv, X.rs1, X.dgvpre, B * Mp, st));
+    if (e->gv_norm_fwd == CMPC_GV_NORM_SAMPLE) CK(cmpc_l2norm_rows_bwd(DT_F32, X.dgv, X.gv, X.rs1, X.dgvpre, B, Mp, M, 0, st));
+    else CK(cmpc_l2norm_all_bwd(X.dgv, X.gv, X.rs1, X.dgvpre, B * Mp, st));
     if (!e->gv_tanh) CK(colsum(st, DT_F32, X.dgvpre, B, Mp, Mp, M, gptr(e, fmt("gv_lang_%sgv_f1/biases", lv))));
     else CK(colsum(st, DT_F32, X.dgvpre, B, Mp, Mp, M, gptr(e, fmt("gv_lang_%sgv_f1/biases", lv)), X.gvpre, X.dgvpre, ACT_TANH));     // X.gvpre holds tanh(...)
     GemmOpt m; m.n_valid = M;
@@ -2538,6 +2544,15 @@ extern "C" int cmpc_set_lanes(cmpc_handle e, int n_lanes) {
     e->cfg.n_lanes = n_lanes;
     return CMPC_OK;
 }
+extern "C" int cmpc_set_gv_norm(cmpc_handle e, int mode) {
+    if (!e) { cmpc_set_error("set_gv_norm: null handle"); return CMPC_EINVAL; }
+    if (mode != CMPC_GV_NORM_BATCH && mode != CMPC_GV_NORM_SAMPLE) {
+        cmpc_set_error("set_gv_norm: mode %d is neither CMPC_GV_NORM_BATCH (0) nor CMPC_GV_NORM_SAMPLE (1)", mode);
+        return CMPC_EINVAL;
+    }
+    e->gv_norm = mode;
+    return CMPC_OK;
+}
 extern "C" int cmpc_kernel_timing(cmpc_handle e, int enable) {
     if (!e) { cmpc_set_error("kernel_timing: null handle"); return CMPC_EINVAL; }
     for (hipEvent_t ev : e->tev) (void)hipEventDestroy(ev);
@@ -2613,6 +2628,7 @@ extern "C" int cmpc_forward(cmpc_handle e, const cmpc_feeds* f, const cmpc_fetch
     e->c2_feed = f->c2; e->im_feed = f->im;
     const int B = e->B, Cp = e->Cp, NL = e->nlev, NX = e->nex;
     e->have_target = f->target_fine != nullptr;
+    e->gv_norm_fwd = e->gv_norm;
     for (auto& d : e->deferred) d.clear();
     e->lv[0].feat = f->c5; e->lv[1].feat = f->c4; e->lv[2].feat = f->c3;
     CK(params_ready(e, main, 0));

@@ -262,6 +262,36 @@ __global__ __launch_bounds__(NTHR) void eval_mask_iu_kernel(MaskArgs a) {
     }
 }
 
+struct OutArgs {
+    const void* map; int H, W; float thresh;
+    unsigned char* out; uint32_t value;
+    cmpc_eval_desc d[CMPC_EVAL_MAX_BATCH];
+    SampleGeo g[CMPC_EVAL_MAX_BATCH];
+};
+
+// eval_mask_iu's decision without a ground truth: value * (resampled binarised map > 0) at the descriptor's size, four pixels per thread
+template <typename T>
+__global__ __launch_bounds__(NTHR) void eval_mask_out_kernel(OutArgs a) {
+    const int b = blockIdx.y;
+    const cmpc_eval_desc d = a.d[b];
+    const SampleGeo g = a.g[b];
+    const T* m = (const T*)a.map + (int64_t)b * a.H * a.W;
+    unsigned char* mo = a.out + d.offset;
+    const int64_t n = (int64_t)d.h * d.w;
+    const bool al = ((uintptr_t)mo & 3) == 0;
+    for (int64_t i4 = ((int64_t)blockIdx.x * NTHR + threadIdx.x) * 4; i4 < n; i4 += (int64_t)gridDim.x * NTHR * 4) {
+        const int k = (int)min((int64_t)4, n - i4);
+        uint32_t pv = 0;
+        for (int j = 0; j < k; ++j) {
+            const int64_t i = i4 + j;
+            const int y = (int)(i / d.w), x = (int)(i - (int64_t)y * d.w);
+            if (pred_at(m, a.H, a.W, a.thresh, g, y + d.top, x + d.left)) pv |= a.value << (8 * j);
+        }
+        if (k == 4 && al) *(uint32_t*)(mo + i4) = pv;
+        else for (int j = 0; j < k; ++j) mo[i4 + j] = (unsigned char)(pv >> (8 * j));
+    }
+}
+
 // resize_and_pad_geometry / resize_and_crop_geometry (hostutil.py): Python's true division, np.round (half to even), int(floor(.) / 2)
 void geometry(int ih, int iw, int oh, int ow, bool pad, int out[4]) {
     const double s = pad ? fmin((double)oh / ih, (double)ow / iw) : fmax((double)oh / ih, (double)ow / iw);
@@ -609,4 +639,23 @@ extern "C" int cmpc_train_prep(const unsigned char* img, int64_t img_bytes, cons
     if (hipMemsetAsync(pos, 0, sizeof(uint64_t) * B, ST) != hipSuccess) { cmpc_set_error("train_prep: hipMemsetAsync"); return CMPC_EHIP; }
     hipLaunchKernelGGL(train_target_kernel, dim3((W + tx - 1) / tx, (H + ty - 1) / ty, B), dim3(NTHR), lds, ST, a);
     return cmpc_check_launch("train_prep");
+}
+
+extern "C" int cmpc_eval_mask_out(const void* map, int map_dt, int B, int H, int W, float thresh, const cmpc_eval_desc* descs_host,
+                                  unsigned char* mask_out, int64_t out_bytes, int value, void* stream) {
+    if (!map || !descs_host || !mask_out) { cmpc_set_error("eval_mask_out: NULL pointer"); return CMPC_EINVAL; }
+    if (map_dt != CMPC_EVAL_F32 && map_dt != CMPC_EVAL_U8) { cmpc_set_error("eval_mask_out: map dtype %d is neither f32 nor u8", map_dt); return CMPC_EINVAL; }
+    if (B <= 0 || B > CMPC_EVAL_MAX_BATCH) { cmpc_set_error("eval_mask_out: B = %d outside 1..%d", B, CMPC_EVAL_MAX_BATCH); return CMPC_EINVAL; }
+    if (H <= 0 || W <= 0 || out_bytes <= 0) { cmpc_set_error("eval_mask_out: bad map size %d x %d or buffer length", H, W); return CMPC_EINVAL; }
+    if (value != 1 && value != 255) { cmpc_set_error("eval_mask_out: value %d is neither 1 nor 255", value); return CMPC_EINVAL; }
+    OutArgs a;
+    const int rc = check_descs("eval_mask_out", descs_host, B, out_bytes, H, W, false, a.g);
+    if (rc) return rc;
+    a.map = map; a.H = H; a.W = W; a.thresh = thresh; a.out = mask_out; a.value = (uint32_t)value;
+    int64_t most = 0;
+    for (int b = 0; b < B; ++b) { a.d[b] = descs_host[b]; most = std::max(most, (int64_t)descs_host[b].h * descs_host[b].w); }
+    const int per_sample = (int)std::max<int64_t>(1, std::min<int64_t>((most + 4 * NTHR - 1) / (4 * NTHR), 2048 / B));
+    if (map_dt == CMPC_EVAL_F32) hipLaunchKernelGGL(eval_mask_out_kernel<float>, dim3(per_sample, B), dim3(NTHR), 0, ST, a);
+    else hipLaunchKernelGGL(eval_mask_out_kernel<unsigned char>, dim3(per_sample, B), dim3(NTHR), 0, ST, a);
+    return cmpc_check_launch("eval_mask_out");
 }

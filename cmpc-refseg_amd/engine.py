@@ -220,6 +220,9 @@ class Engine:
     def set_lanes(self, n: int):
         _lib.call("cmpc_set_lanes", self.h, int(n))
 
+    def set_gv_norm(self, mode: int):
+        _lib.call("cmpc_set_gv_norm", self.h, int(mode))
+
     def grad_buckets(self):
         """[[(offset, count), ...], ...]: the ranges of the flat gradient buffer in the order they become final during backward."""
         out, n, offs, cnts = [], C.c_int(), (C.c_int64 * 4)(), (C.c_int64 * 4)()

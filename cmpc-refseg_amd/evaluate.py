@@ -20,7 +20,8 @@ restatement of skimage.transform.resize (parity-unpinned against scikit-image it
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+import contextlib
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -184,6 +185,65 @@ def mask_iu(score_map, gt_masks, thresh: float = 1e-9, want_masks: bool = False,
     return iu, [mo[d.offset: d.offset + d.h * d.w].view(d.h, d.w) for d in descs]
 
 
+def masks_out(score_map, sizes: Sequence[Tuple[int, int]], thresh: float = 1e-9, value: int = 1, out: torch.Tensor = None):
+    """value * (resize_and_crop(score_map[b] >= thresh, oh, ow) > 0) per sample on the device, with no ground truth (cmpc_eval_mask_out):
+    mask_iu's decision at any output size.  score_map as for mask_iu; sizes: one (oh, ow) per sample; value 1 or 255.  Returns
+    (buf, descs): a flat uint8 device buffer (`out` when given: it must hold the packed length) and the descriptors whose 16-byte
+    aligned offsets locate sample b's [oh, ow] mask in it (unpack_masks).  Bytes between the masks are not written.
+
+    The rule is "resampled value > 0" (trainval_model.py:245 with compute_mask_IU), as everywhere in this package.  test.py:308 casts the
+    resampled float map with .astype('uint8') instead, which keeps only values that are exactly >= 1.0: with this resampler an all-ones
+    320 x 320 map comes out 98.4 % foreground at (240, 427) and 0.19 % at (166, 250).  That is an accident of rounding, not reproduced."""
+    m = score_map
+    if not torch.is_tensor(m) or m.device.type != "cuda":
+        raise ValueError("score_map must be a device tensor")
+    if m.dim() == 4 and m.shape[3] == 1:
+        m = m[..., 0]
+    if m.dim() != 3 or m.dtype not in (torch.float32, torch.uint8):
+        raise ValueError("score_map must be [B, H, W] float32 or uint8, got %s %s" % (m.dtype, tuple(m.shape)))
+    m = m.contiguous()
+    B, H, W = m.shape
+    if len(sizes) != B:
+        raise ValueError("%d sizes for a batch of %d maps" % (len(sizes), B))
+    descs, nbytes = plan_masks(sizes, H, W)
+    dev = m.device
+    with torch.cuda.device(dev):
+        buf = out if out is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        if buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() < nbytes or not buf.is_contiguous() or buf.device != dev:
+            raise ValueError("out must be a contiguous uint8 device buffer of at least %d bytes" % nbytes)
+        dt = _lib.EVAL_F32 if m.dtype == torch.float32 else _lib.EVAL_U8
+        _lib.call("cmpc_eval_mask_out", m.data_ptr(), dt, B, H, W, float(thresh), descs, buf.data_ptr(), buf.numel(), int(value),
+                  torch.cuda.current_stream(dev).cuda_stream)
+    return buf, descs
+
+
+def unpack_masks(buf, descs) -> list:
+    """The [h, w] views of a packed mask buffer (device tensor or NumPy array) at its descriptors' offsets."""
+    if torch.is_tensor(buf):
+        return [buf[d.offset: d.offset + d.h * d.w].view(d.h, d.w) for d in descs]
+    return [buf[d.offset: d.offset + d.h * d.w].reshape(d.h, d.w) for d in descs]
+
+
+def check_gv_norm(mode: Optional[str], allow_none: bool = True) -> Optional[str]:
+    if (mode is None and allow_none) or mode in _lib.GV_NORMS:
+        return mode
+    raise ValueError("gv_norm must be %s'batch' or 'sample', got %r" % ("None, " if allow_none else "", mode))
+
+
+@contextlib.contextmanager
+def gv_norm_scope(model, mode: Optional[str]):
+    """The model's gv_lang norm set to `mode` for the forward passes inside, restored afterwards; None leaves the model as it is."""
+    if mode is None:
+        yield
+        return
+    prev = model.gv_norm
+    model.set_gv_norm(mode)
+    try:
+        yield
+    finally:
+        model.set_gv_norm(prev)
+
+
 def _metrics(iu: np.ndarray, thresholds: Sequence[float]) -> Dict[str, float]:
     # hostutil.SegEval's arithmetic, in sample order
     cum_I = cum_U = 0
@@ -211,20 +271,24 @@ def _pad_to(items: list, B: int) -> list:
     return list(items) + [items[0]] * (B - len(items))
 
 
-def predict_masks(model, ids, seq_len, images) -> List[np.ndarray]:
+def predict_masks(model, ids, seq_len, images, gv_norm: Optional[str] = None) -> List[np.ndarray]:
     """Inference only: the reference's `predicts` (resize_and_crop(up >= 1e-9) at each image's original size) for up to
-    model.batch_size samples, as host uint8 {0, 1} arrays."""
+    model.batch_size samples, as host uint8 {0, 1} arrays.  gv_norm: None leaves the model's gv_lang norm as it is; "sample" / "batch" set
+    it for this call and restore it (LSTM_model.set_gv_norm: with "sample" the masks are those of the reference's batch-1 loop, whatever
+    the batch holds; with "batch" a sample's mask depends on its batch mates and on the pads of a short batch)."""
     _check_model(model)
+    check_gv_norm(gv_norm)
     images = list(images)
     n, B = len(images), model.batch_size
     if n == 0 or n > B:
         raise ValueError("predict_masks: 1..%d samples per call, got %d" % (B, n))
     ids, seq_len = np.asarray(ids, dtype=np.int32).reshape(n, -1), np.asarray(seq_len, dtype=np.int32).reshape(n)
     feed, _ = prepare_images(_pad_to(images, B), model.H, model.W, model.device)
-    up = model.forward(np.concatenate([ids, np.repeat(ids[:1], B - n, 0)]), feed, np.concatenate([seq_len, np.repeat(seq_len[:1], B - n)]))["up"]
-    zeros = [np.zeros(np.asarray(im).shape[:2], dtype=np.uint8) for im in images]
-    _, masks = mask_iu(up[:n].float(), zeros, 1e-9, want_masks=True)
-    return [mk.cpu().numpy() for mk in masks]
+    with gv_norm_scope(model, gv_norm):
+        up = model.forward(np.concatenate([ids, np.repeat(ids[:1], B - n, 0)]), feed, np.concatenate([seq_len, np.repeat(seq_len[:1], B - n)]))["up"]
+    buf, descs = masks_out(up[:n].float(), [np.asarray(im).shape[:2] for im in images], 1e-9)
+    host = buf.cpu().numpy()
+    return [mk.copy() for mk in unpack_masks(host, descs)]
 
 
 def _check_dcrf_method(method: str) -> str:
@@ -239,11 +303,14 @@ class Evaluator:
     dcrf, DenseCRF on each sample's sigm / proc_im -> mask_iu on the argmax).  result() flushes a partial last batch (padded by
     repeating a sample; pads are never counted) and returns hostutil.SegEval.result()'s keys plus `samples` (and `dcrf_`-prefixed
     metrics with dcrf).  dcrf_method: "exact" (one cmpc_dense_crf call per sample) or "lattice" (the batch's masks from one
-    cmpc_dense_crf_lattice call, crf.py)."""
+    cmpc_dense_crf_lattice call, crf.py).  gv_norm: None leaves the model's gv_lang norm as it is (by default the batch-wide norm of the
+    training graph: a sample's (I, U) then depends on its batch mates and on the pads of the last batch); "sample" gives every sample the
+    result of the reference's batch-1 `-m test` loop; either value is set around each forward pass and the model's own mode restored."""
 
     def __init__(self, model, thresholds: Sequence[float] = (.5, .6, .7, .8, .9), dcrf: bool = False, score_thresh: float = 1e-9,
-                 dcrf_method: str = "exact"):
+                 dcrf_method: str = "exact", gv_norm: Optional[str] = None):
         _check_model(model)
+        self.gv_norm = check_gv_norm(gv_norm)
         self.model, self.thresholds, self.dcrf, self.score_thresh = model, tuple(thresholds), bool(dcrf), float(score_thresh)
         self.dcrf_method = _check_dcrf_method(dcrf_method)
         self.B, self.H, self.W = model.batch_size, model.H, model.W
@@ -277,7 +344,8 @@ class Evaluator:
         sl = np.array([s[1] for s in q], dtype=np.int32)
         with torch.cuda.device(m.device):
             feed, proc = prepare_images([s[2] for s in q], self.H, self.W, m.device)
-            out = m.forward(ids, feed, sl)
+            with gv_norm_scope(m, self.gv_norm):
+                out = m.forward(ids, feed, sl)
             gts = [s[3] for s in q[:n]]
             self._grow(self.n + n)
             mask_iu(out["up"][:n].float(), gts, self.score_thresh, out=self.iu[self.n: self.n + n])

@@ -126,6 +126,7 @@ class LSTM_model(object):
             n_lanes = 3 if int(os.environ.get("CMPC_STREAMS", "3")) > 1 else 1
         with torch.cuda.device(self.device):
             self.eng = Engine(self.cfg, self.dt, self.device, n_lanes=n_lanes)
+            self.gv_norm = "batch"                        # set_gv_norm()
             self.store = self.eng                         # parameter / gradient accessors (state_dict, grad_dict, p, g, step)
             if head_params is None:
                 head_params = self._init_params(seed)
@@ -226,6 +227,16 @@ class LSTM_model(object):
         torch.cuda.synchronize(self.device)
         self.eng.set_lanes(n)
         self.bb_stream, self.opt_stream = self._side if n > 1 else (None, None)
+
+    def set_gv_norm(self, mode: str):
+        """What l2_normalize(gv_lang) (CMPC_model.py:241, no axis) runs over, from the next forward pass on.  "batch" (the default): the
+        whole [B, M] tensor, the graph at batch_size = B -- what training runs.  "sample": each sample alone, the graph at batch_size = 1 --
+        what every inference loop of the reference runs (trainval_model.py:178-182, test.py:219-226); a sample's result then does not depend
+        on its batch mates.  The current mode is `self.gv_norm`.  Only the handle's host state changes: nothing synchronises."""
+        if mode not in _lib.GV_NORMS:
+            raise ValueError("gv_norm must be 'batch' or 'sample', got %r" % (mode,))
+        self.eng.set_gv_norm(_lib.GV_NORMS[mode])
+        self.gv_norm = mode
 
     # ------------------------------------------------------------------------------------------
     def _check_feeds(self, words, im, seq_len, target=None):

@@ -1,0 +1,269 @@
+"""Segment a video per referring expression: the reference's Refer-YouTube-VOS prediction loop (test.py:250-329) on the GPU.
+
+For every video test.py runs every expression over every frame, one sample per sess.run on a batch-1 graph, and writes one mask per
+(expression, frame) at half the frame's size.  Here
+
+    seg = FrameSegmenter(model, vocab)
+    for e, f, mask in seg.run(frames, expressions):        # mask: host uint8 [oh, ow] in {0, value}
+
+does the same work in batches of model.batch_size frames:
+
+    upload + cmpc_eval_prep + backbone      once per frame batch (the backbone does not see the sentence: 69 GMAC per frame saved per
+                                            further expression)
+    model.head on those taps                once per (frame batch, expression)
+    cmpc_eval_mask_out + one copy           the batch's masks, sigm >= threshold resized and cropped to out_size(h, w), into a ring of
+                                            pinned host buffers behind an event
+
+with gv_norm="sample" by default (LSTM_model.set_gv_norm), so that every (expression, frame) pair gets what the batch-1 loop computes,
+whatever else shares its batch -- the pads of a short last batch included.
+
+The mask is "resampled value > 0" of the binarised map, the rule of trainval_model.py:245 and of every path in this package.
+test.py:308 casts the resampled float map with .astype('uint8') instead, which keeps only values that are exactly >= 1.0 -- an accident
+of rounding (an all-ones 320 x 320 map comes out 98.4 % foreground at (240, 427) and 0.19 % at (166, 250)); it is not reproduced.
+
+Order on the device.  The graphed backbone alternates two static output slots (LSTM_model._backbone_graphed), and features_async makes
+the backbone stream wait for everything enqueued on the caller's stream so far.  run() enqueues frame batch n + 1's upload, prep and
+backbone BEFORE batch n's heads: that pass runs beside batch n's heads, and it rewrites the slot of batch n - 1, whose heads were all
+enqueued before it.  The pass after it is enqueued behind batch n's heads in the same way, so no tap is rewritten while a head may still
+read it.  Only the caller's thread talks to HIP; nothing allocates and nothing synchronises the device in the
+steady state: the host waits only on the event of the ring slot it is about to hand out or reuse.
+"""
+from __future__ import annotations
+
+from collections import deque
+from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib, hostutil as HU
+from .evaluate import MAX_BATCH, _check_dcrf_method, _images_u8, check_gv_norm, gv_norm_scope, plan_masks, plan_prep
+
+
+def half_size(h: int, w: int) -> Tuple[int, int]:
+    """test.py:308: masks are written at (h // 2, w // 2)."""
+    return h // 2, w // 2
+
+
+def plan_batches(n: int, B: int) -> List[List[int]]:
+    """Frame indices of each batch of B: consecutive frames; a short last batch is padded by repeating its first frame."""
+    if n <= 0 or B <= 0:
+        raise ValueError("plan_batches: %d frames in batches of %d" % (n, B))
+    out = []
+    for s in range(0, n, B):
+        idx = list(range(s, min(s + B, n)))
+        out.append(idx + [idx[0]] * (B - len(idx)))
+    return out
+
+
+def check_expression(i: int, ex, vocab, T: int) -> Tuple[np.ndarray, int]:
+    """A sentence (tokenised as test.py:267 does, hostutil.preprocess_sentence_lstm) or an (ids, seq_len) pair -> (END-padded int32 ids
+    [T], seq_len).  Raises ValueError naming expression `i`."""
+    if isinstance(ex, str):
+        if vocab is None:
+            raise ValueError("expression %d: a sentence needs the vocabulary (FrameSegmenter(vocab=...)); pass (ids, seq_len) otherwise" % i)
+        ids, n = HU.preprocess_sentence_lstm(ex, vocab, T)
+        if n == 0:
+            raise ValueError("expression %d: empty sentence (the model needs at least one word)" % i)
+        return np.asarray(ids, dtype=np.int32), n
+    try:
+        ids, n = ex
+    except (TypeError, ValueError):
+        raise ValueError("expression %d: expected a sentence or an (ids, seq_len) pair, got %r" % (i, type(ex).__name__)) from None
+    ids = np.asarray(ids)
+    if ids.ndim != 1 or ids.shape[0] != T or not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError("expression %d: ids must be integers [%d], got %s %s" % (i, T, ids.dtype, ids.shape))
+    n = int(n)
+    if not 1 <= n <= T:
+        raise ValueError("expression %d: seq_len %d outside 1..%d" % (i, n, T))
+    return ids.astype(np.int32), n
+
+
+class _DeviceStage:
+    """The device half of FrameSegmenter.  All buffers are allocated once (the pinned ring and the device mask buffer grow only when a
+    batch needs more bytes than any before it): two feed / proc_im sets that alternate with the frame batches, one device mask buffer,
+    `nslots` pinned host buffers with an event each.  Everything is enqueued on the caller's current stream."""
+
+    def __init__(self, model, nslots: int, threshold: float, value: int, dcrf: bool, dcrf_method: str):
+        import torch
+        from .evaluate import _Staging
+        self.torch = torch
+        self.model, self.threshold, self.value, self.dcrf, self.dcrf_method = model, threshold, value, dcrf, dcrf_method
+        self.dev = model.device
+        B, H, W = model.batch_size, model.H, model.W
+        with torch.cuda.device(self.dev):
+            self.staging = _Staging(self.dev)
+            self.feed = [torch.empty(B, H, W, 3, dtype=torch.float32, device=self.dev) for _ in range(2)]
+            self.proc = [torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.dev) for _ in range(2)]
+            self.events = [torch.cuda.Event() for _ in range(nslots)]
+        self.nslots = nslots
+        self.host: List = [None] * nslots
+        self.mask_dev = None
+        self.k = 0
+        self.words = []
+
+    def reserve(self, nbytes: int):
+        """Room for `nbytes` of packed masks in every ring slot and in the device buffer."""
+        torch = self.torch
+        if self.mask_dev is not None and self.mask_dev.numel() >= nbytes:
+            return
+        cap = max(nbytes, 1 << 20)
+        torch.cuda.synchronize(self.dev)               # a copy into the old buffers may be in flight (growth only: not the steady state)
+        with torch.cuda.device(self.dev):
+            self.mask_dev = torch.empty(cap, dtype=torch.uint8, device=self.dev)
+            old, self.host = self.host, [torch.empty(cap, dtype=torch.uint8, pin_memory=True) for _ in range(self.nslots)]
+        for o, h in zip(old, self.host):               # results not handed out yet move with their slot
+            if o is not None:
+                h[: o.numel()].copy_(o)
+
+    def set_expressions(self, exprs: Sequence[Tuple[np.ndarray, int]]):
+        torch, B = self.torch, self.model.batch_size
+        with torch.cuda.device(self.dev):
+            self.words = [(torch.from_numpy(np.repeat(ids[None], B, 0)).to(self.dev), torch.full((B,), n, dtype=torch.int32).to(self.dev))
+                          for ids, n in exprs]
+
+    def begin(self, images: List[np.ndarray]):
+        """Upload, cmpc_eval_prep and the backbone pass of one (padded) frame batch; returns the token segment() takes."""
+        torch, m = self.torch, self.model
+        k, self.k = self.k, 1 - self.k
+        descs, nbytes = plan_prep([a.shape for a in images], m.H, m.W)
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            src = self.staging.upload(images, descs, nbytes)
+            feed, proc = self.feed[k], self.proc[k]
+            _lib.call("cmpc_eval_prep", src.data_ptr(), nbytes, descs, len(images), m.H, m.W, proc.data_ptr(), feed.data_ptr(),
+                      torch.cuda.current_stream(self.dev).cuda_stream)
+            feats, done = m.features_async(feed)
+        return feats, done, feed, proc
+
+    def segment(self, token, e: int, descs, nbytes: int, slot: int):
+        """Head of expression e on the batch's taps, the masks of its first len(descs) frames into ring slot `slot`."""
+        torch, m = self.torch, self.model
+        feats, done, feed, proc = token
+        n = len(descs)
+        words, sl = self.words[e]
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            o = m.head(feats, words, sl, after=done, im=feed)
+            sigm = o["sigm"].float().reshape(m.batch_size, m.H, m.W)
+            if self.dcrf:
+                from . import crf
+                score, thr = crf.dense_crf_batch(sigm[:n], proc[:n], device=self.dev, method=self.dcrf_method), 0.5
+            else:
+                score, thr = sigm, self.threshold
+            dt = _lib.EVAL_F32 if score.dtype == torch.float32 else _lib.EVAL_U8
+            _lib.call("cmpc_eval_mask_out", score.data_ptr(), dt, n, m.H, m.W, float(thr), descs, self.mask_dev.data_ptr(),
+                      self.mask_dev.numel(), self.value, torch.cuda.current_stream(self.dev).cuda_stream)
+            self.host[slot][:nbytes].copy_(self.mask_dev[:nbytes], non_blocking=True)
+            self.events[slot].record(torch.cuda.current_stream(self.dev))
+
+    def done(self, slot: int) -> bool:
+        return self.events[slot].query()
+
+    def wait(self, slot: int):
+        self.events[slot].synchronize()
+
+    def view(self, slot: int) -> np.ndarray:
+        return self.host[slot].numpy()
+
+
+class FrameSegmenter:
+    """test.py:250-329 batched on the GPU (module docstring).  run(frames, expressions) yields (e, f, mask) for every expression index e
+    and frame index f: frame batches in order, within a batch expressions in order, within those frames in order.
+
+    frames: original-size uint8 arrays [h, w, 3] or [h, w] (any iterable: decoded lazily, one batch ahead); expressions: sentences
+    (needs `vocab`) or (END-padded ids [T], seq_len) pairs.  mask = value * (resize_and_crop(sigm >= threshold, *out_size(h, w)) > 0),
+    thresholding the float32 sigm itself (test.py:307); with dcrf, the same resampling of the DenseCRF argmax on sigm / proc_im
+    (test.py:309-322, crf.dense_crf_batch).  gv_norm: "sample" (default: the loop this replaces is batch 1) or "batch"; set for the
+    run, the model's own mode restored when the generator ends or is closed.  depth: (frame batch, expression) results in flight behind
+    the one being handed out (depth + 1 pinned slots).  copy=False yields views of the pinned slot, valid until the next iteration."""
+
+    def __init__(self, model, vocab=None, threshold: float = 0.5, out_size: Callable[[int, int], Tuple[int, int]] = half_size, value: int = 255,
+                 dcrf: bool = False, dcrf_method: str = "lattice", gv_norm: str = "sample", depth: int = 2, copy: bool = True, _stage=None):
+        if getattr(model, "video", False):
+            raise ValueError("FrameSegmenter: the video model (CMPC_video_mm_tgraph_allvec) is not supported: it takes a clip per forward pass")
+        if model.batch_size > MAX_BATCH:
+            raise ValueError("FrameSegmenter: model.batch_size %d > %d" % (model.batch_size, MAX_BATCH))
+        if value not in (1, 255):
+            raise ValueError("value must be 1 or 255, got %r" % (value,))
+        if int(depth) < 1:
+            raise ValueError("depth must be >= 1, got %r" % (depth,))
+        self.model, self.vocab, self.threshold, self.out_size, self.value = model, vocab, float(threshold), out_size, int(value)
+        self.dcrf, self.dcrf_method = bool(dcrf), _check_dcrf_method(dcrf_method)
+        self.gv_norm = check_gv_norm(gv_norm, allow_none=False)
+        self.depth, self.copy = int(depth), bool(copy)
+        self.B, self.T, self.H, self.W = model.batch_size, model.num_steps, model.H, model.W
+        self.nslots = self.depth + 1
+        self.stage = _stage if _stage is not None else _DeviceStage(model, self.nslots, self.threshold, self.value, self.dcrf, self.dcrf_method)
+
+    def _batches(self, frames: Iterable) -> Iterator[Tuple[int, List[np.ndarray]]]:
+        """(index of the first frame, the validated frames) of every batch of B, read lazily."""
+        first, cur = 0, []
+        for f, im in enumerate(frames):
+            a = np.asarray(im)
+            try:
+                cur.extend(_images_u8([a]))
+            except ValueError as e:
+                raise ValueError("frame %d: %s" % (f, str(e).split(": ", 1)[-1])) from None
+            if len(cur) == self.B:
+                yield first, cur
+                first, cur = f + 1, []
+        if cur:
+            yield first, cur
+
+    def _plan(self, first: int, ims: List[np.ndarray]):
+        sizes = []
+        for i, a in enumerate(ims):
+            oh, ow = self.out_size(int(a.shape[0]), int(a.shape[1]))
+            if int(oh) < 1 or int(ow) < 1:
+                raise ValueError("frame %d: out_size(%d, %d) = (%d, %d) is empty" % (first + i, a.shape[0], a.shape[1], oh, ow))
+            sizes.append((int(oh), int(ow)))
+        descs, nbytes = plan_masks(sizes, self.H, self.W)
+        return descs, nbytes
+
+    def run(self, frames: Iterable, expressions: Sequence) -> Iterator[Tuple[int, int, np.ndarray]]:
+        exprs = [check_expression(i, ex, self.vocab, self.T) for i, ex in enumerate(expressions)]
+        if not exprs:
+            raise ValueError("FrameSegmenter.run: no expressions")
+        st = self.stage
+        free = deque(range(self.nslots))
+        pending = deque()                          # (slot, e, first frame, descs) in enqueue order = yield order
+
+        def hand_out(block: bool):
+            """Yield the masks of the oldest result(s) whose event has completed (waiting for the oldest one if `block`)."""
+            while pending and (block or st.done(pending[0][0])):
+                slot, e, first, descs = pending.popleft()
+                st.wait(slot)
+                host = st.view(slot)
+                for i, d in enumerate(descs):
+                    mk = host[d.offset: d.offset + d.h * d.w].reshape(d.h, d.w)
+                    yield e, first + i, (mk.copy() if self.copy else mk)
+                free.append(slot)                  # only now: the caller has moved past the slot's last mask
+                block = False
+
+        with gv_norm_scope(self.model, self.gv_norm):
+            st.set_expressions(exprs)
+            it = self._batches(frames)
+
+            def begin_next():
+                nxt = next(it, None)
+                if nxt is None:
+                    return None
+                first, ims = nxt
+                descs, nbytes = self._plan(first, ims)
+                st.reserve(nbytes)
+                return first, descs, nbytes, st.begin(ims + [ims[0]] * (self.B - len(ims)))
+
+            cur = begin_next()
+            if cur is None:
+                raise ValueError("FrameSegmenter.run: no frames")
+            while cur is not None:
+                nxt = begin_next()                 # the next batch's backbone pass goes in ahead of this batch's heads (module docstring)
+                first, descs, nbytes, token = cur
+                for e in range(len(exprs)):
+                    if not free:
+                        yield from hand_out(True)
+                    slot = free.popleft()
+                    st.segment(token, e, descs, nbytes, slot)
+                    pending.append((slot, e, first, descs))
+                    yield from hand_out(False)
+                cur = nxt
+            while pending:
+                yield from hand_out(True)

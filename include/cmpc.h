@@ -507,6 +507,15 @@ int cmpc_operand_info(cmpc_handle h, const char* key, int64_t* byte_off, int* dt
 int cmpc_phase_marks(cmpc_handle h, int enable);
 int cmpc_phase_marks_read(cmpc_handle h, int index, const char** name, float* ms_since_first);
 int cmpc_set_lanes(cmpc_handle h, int n_lanes);      /* 1 or 3; takes effect from the next cmpc_forward */
+/* Which elements the l2_normalize of gv_lang (CMPC_model.py:241, tf.nn.l2_normalize with no axis; the same line in the v5 files) runs
+ * over.  CMPC_GV_NORM_BATCH (the default): the whole [B, M] tensor -- the graph built at batch_size = B, which is what training runs.
+ * CMPC_GV_NORM_SAMPLE: every sample alone -- the same line at batch_size = 1, which is what every inference script of the reference
+ * runs (trainval_model.py:178-182, test.py:219-226); a sample's result then does not depend on its batch mates.  At B = 1 (the video
+ * model) the two coincide.  Takes effect from the next cmpc_forward; cmpc_backward differentiates whatever its forward computed.  Works
+ * on a planning-only handle.  Any other mode: CMPC_EINVAL. */
+#define CMPC_GV_NORM_BATCH 0
+#define CMPC_GV_NORM_SAMPLE 1
+int cmpc_set_gv_norm(cmpc_handle h, int mode);
 int cmpc_kernel_timing(cmpc_handle h, int enable);
 int cmpc_kernel_timing_read(cmpc_handle h, double* ms, double* flops, double* bytes, int64_t* launches);
 /* Launch trace without a profiler (process-wide): while enabled, every launch of this library is followed by a hipEvent on `stream`, so that
@@ -560,6 +569,14 @@ int cmpc_eval_prep(const unsigned char* src, int64_t src_bytes, const cmpc_eval_
  * gt_bytes long).  mask_out: NULL, or a buffer laid out like gt that receives the predicted mask at the original size (uint8 {0, 1}). */
 int cmpc_eval_mask_iu(const void* map, int map_dt, int B, int H, int W, float thresh, const unsigned char* gt, int64_t gt_bytes,
                       const cmpc_eval_desc* descs_host, uint64_t* iu, unsigned char* mask_out, void* stream);
+/* Masks without a ground truth: mask_out[d.offset + y * d.w + x] = value * (resize_and_crop(map[b] >= thresh, d.h, d.w)[y, x] > 0), the
+ * decision of cmpc_eval_mask_iu at any output size d.h x d.w (the frame's size, or test.py:308's (h // 2, w // 2)); descriptors as for
+ * cmpc_eval_mask_iu (c = 1, resize_and_crop_geometry(H, W, d.h, d.w)), offsets into mask_out (out_bytes long).  value: 1 or 255.
+ * Writes the d.h * d.w bytes of every sample and nothing else; no counters, no memset.  The rule is "resampled value > 0"
+ * (trainval_model.py:245), not test.py:308's .astype('uint8') of the resampled float map, which keeps only values that round to
+ * exactly 1.0. */
+int cmpc_eval_mask_out(const void* map, int map_dt, int B, int H, int W, float thresh, const cmpc_eval_desc* descs_host,
+                       unsigned char* mask_out, int64_t out_bytes, int value, void* stream);
 
 /* ---- Training feed from raw samples (util/data_reader_refvos.py:27-46, build_batches.py:62-75): the image half is cmpc_eval_prep's
  *      kernel, the mask half cuts the object out of the annotation and resamples it.  One annotation descriptor per sample (HOST memory,
