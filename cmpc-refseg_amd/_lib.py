@@ -122,6 +122,7 @@ class EvalDesc(C.Structure):
 
 EVAL_MAX_BATCH = 32      # CMPC_EVAL_MAX_BATCH
 EVAL_F32, EVAL_U8 = 0, 1
+TAPS_MAX_LEVELS, TAPS_MAX_FRAMES = 3, 8      # CMPC_TAPS_MAX_*
 GV_NORM_BATCH, GV_NORM_SAMPLE = 0, 1      # CMPC_GV_NORM_*
 GV_NORMS = {"batch": GV_NORM_BATCH, "sample": GV_NORM_SAMPLE}
 
@@ -251,6 +252,7 @@ SIGNATURES = {
     "cmpc_eval_mask_iu": [_P, _I, _I, _I, _I, _F, _P, _L, C.POINTER(EvalDesc), _P, _P, _P],
     "cmpc_eval_mask_out": [_P, _I, _I, _I, _I, _F, C.POINTER(EvalDesc), _P, _L, _I, _P],
     "cmpc_train_prep": [_P, _L, C.POINTER(EvalDesc), _P, _L, C.POINTER(TrainDesc), _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "cmpc_taps_copy": [_I, _PP, _PP, C.POINTER(_L), _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _P],
     "cmpc_launch_trace": [_I, _P],
     "cmpc_launch_trace_read": [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_L)],
     "cmpc_kernel_timing": [_P, _I],

@@ -1,4 +1,5 @@
-"""Segment a video per referring expression: the reference's Refer-YouTube-VOS prediction loop (test.py:250-329) on the GPU.
+"""Segment a video per referring expression: the reference's Refer-YouTube-VOS prediction loop (test.py:250-329) on the GPU, and, for the
+video model, the video driver's per-clip prediction over every frame of a video (ClipSegmenter, at the end of this file).
 
 For every video test.py runs every expression over every frame, one sample per sess.run on a batch-1 graph, and writes one mask per
 (expression, frame) at half the frame's size.  Here
@@ -267,3 +268,320 @@ class FrameSegmenter:
                 cur = nxt
             while pending:
                 yield from hand_out(True)
+
+
+# ---- CMPC_video_mm_tgraph_allvec over whole videos (CMPC_video/trainval_video.py:186-253 applied to every frame) --------------------------
+CLIP_LOOKAHEAD = 1             # ClipSegmenter(lookahead=None): backbone batches enqueued ahead of the heads that need them
+
+
+def full_size(h: int, w: int) -> Tuple[int, int]:
+    """trainval_video.py:225: the video driver resamples to the frame's own size."""
+    return h, w
+
+
+def clip_window(f: int, n_frames: int, frames: int = 16) -> List[int]:
+    """The clip of frame f (0-based) of a video of n_frames as build_A2D_batches.py:150-167 forms it: positions f - frames // 2 + k,
+    k = 0..frames-1, each clamped to the video.  Position frames // 2 is f itself."""
+    if not 0 <= f < n_frames:
+        raise ValueError("clip_window: frame %d outside a video of %d frames" % (f, n_frames))
+    return [min(max(f - frames // 2 + k, 0), n_frames - 1) for k in range(frames)]
+
+
+def sampled_frames(f: int, n_frames: int, frames: int = 16) -> List[int]:
+    """The frames of clip_window(f) that the graph reads (model.FRAME_IDX; vid:70): f-8, f-4, f, f+4, f+7 for 16 frames, clamped."""
+    from .model import FRAME_IDX
+    w = clip_window(f, n_frames, frames)
+    return [w[k] for k in FRAME_IDX]
+
+
+def _reach(frames: int) -> Tuple[int, int]:
+    """How far a clip reaches behind and ahead of its own frame."""
+    return frames // 2, frames - 1 - frames // 2
+
+
+def min_ring(frames: int = 16, lookahead: int = CLIP_LOOKAHEAD) -> int:
+    """The smallest ring of cached frames ClipSegmenter can run with.  The backbone takes frames in batches of B = len(FRAME_IDX).  With
+    f the oldest frame whose heads are not all enqueued, run() enqueues batches up to the one that holds frame f + ahead (ahead =
+    frames - 1 - frames // 2, the newest frame f's clip reads) plus `lookahead` more: a batch's first frame s is at most
+    f + ahead + B * lookahead.  The batch writes slots s .. s + B - 1 and so evicts frames up to s + B - 1 - ring, which must all be older
+    than f - frames // 2, the oldest frame a head not yet enqueued reads: ring >= ahead + B * lookahead + B + frames // 2 =
+    frames - 1 + B * (lookahead + 1): 20, 25, 30 for 16-frame clips and a lookahead of 0, 1, 2."""
+    from .model import FRAME_IDX
+    if frames <= max(FRAME_IDX) or int(lookahead) < 0:
+        raise ValueError("min_ring: frames = %r (the graph reads clip position %d), lookahead = %r" % (frames, max(FRAME_IDX), lookahead))
+    return frames - 1 + len(FRAME_IDX) * (int(lookahead) + 1)
+
+
+class _ClipStage:
+    """The device half of ClipSegmenter; everything that touches HIP.  Allocated once: one feed / proc_im set, the ring of cached taps
+    (three levels, `ring` frames each; a proc_im ring with dcrf), the head's contiguous [5, h, w, C] inputs, one event per backbone batch
+    in flight, one device mask buffer and `nslots` pinned host buffers with an event each (these two grow only when a frame needs more
+    bytes than any before it).
+
+    Streams.  Upload, cmpc_eval_prep, the graphed backbone and the scatter into the ring run on the model's backbone stream;
+    features_async makes that stream wait for everything enqueued on the caller's stream so far (the gathers that read the slots this
+    batch evicts among it), and the batch's event is recorded behind the scatter.  Gathers, heads, cmpc_eval_mask_out and the copies to
+    the pinned ring run on the caller's stream; a gather waits for the event of the newest batch its clip reads."""
+
+    def __init__(self, model, ring: int, nslots: int, score: str, threshold: float, value: int, dcrf: bool, dcrf_method: str):
+        import ctypes
+        import torch
+        from .evaluate import _Staging
+        from .model import FRAME_IDX
+        self.torch, self.C = torch, ctypes
+        self.model, self.score, self.threshold, self.value, self.dcrf, self.dcrf_method = model, score, threshold, value, dcrf, dcrf_method
+        self.dev = model.device
+        self.ring, self.nslots, self.B = ring, nslots, len(FRAME_IDX)
+        B, H, W = self.B, model.H, model.W
+        if dcrf and (H * W * 3) % 16:
+            raise ValueError("ClipSegmenter(dcrf=True): H * W * 3 = %d bytes of proc_im per frame is not a multiple of 16" % (H * W * 3))
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            self.staging = _Staging(self.dev)
+            self.feed = torch.empty(B, H, W, 3, dtype=torch.float32, device=self.dev)
+            self.proc = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.dev)
+            taps = model.features(torch.zeros(B, H, W, 3, dtype=torch.float32, device=self.dev))       # shapes and dtype of the three levels
+            self.cache = [torch.empty((ring,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.dev) for t in taps]
+            self.gathered = [torch.empty_like(t) for t in taps]
+            self.proc_ring = torch.empty(ring, H, W, 3, dtype=torch.uint8, device=self.dev) if dcrf else None
+            self.batch_ev = [torch.cuda.Event() for _ in range(ring // B + 2)]
+            self.events = [torch.cuda.Event() for _ in range(nslots)]
+        self.bytes = [t[0].numel() * t.element_size() for t in taps]
+        for b in self.bytes:
+            if b % 16:
+                raise ValueError("ClipSegmenter: a frame's tap block of %d bytes is not a multiple of 16" % b)
+        self.host: List = [None] * nslots
+        self.mask_dev = None
+        self.words = []
+        # argument arrays of cmpc_taps_copy, built once
+        vp, i64 = ctypes.c_void_p * 3, ctypes.c_int64 * 3
+        self._cache_p = vp(*[t.data_ptr() for t in self.cache])
+        self._gath_p = vp(*[t.data_ptr() for t in self.gathered])
+        self._bytes = i64(*self.bytes)
+        self._idx_a, self._idx_b = (ctypes.c_int * _lib.TAPS_MAX_FRAMES)(), (ctypes.c_int * _lib.TAPS_MAX_FRAMES)()
+        self._seq = (ctypes.c_int * _lib.TAPS_MAX_FRAMES)(*range(_lib.TAPS_MAX_FRAMES))
+        self._proc_bytes = (ctypes.c_int64 * 1)(H * W * 3)
+
+    def reserve(self, nbytes: int):
+        """Room for `nbytes` of packed masks (one frame, every expression) in every ring slot and in the device buffer."""
+        torch = self.torch
+        if self.mask_dev is not None and self.mask_dev.numel() >= nbytes:
+            return
+        cap = max(nbytes, 1 << 20)
+        torch.cuda.synchronize(self.dev)               # a copy into the old buffers may be in flight (growth only: not the steady state)
+        with torch.cuda.device(self.dev):
+            self.mask_dev = torch.empty(cap, dtype=torch.uint8, device=self.dev)
+            old, self.host = self.host, [torch.empty(cap, dtype=torch.uint8, pin_memory=True) for _ in range(self.nslots)]
+        for o, h in zip(old, self.host):               # results not handed out yet move with their slot
+            if o is not None:
+                h[: o.numel()].copy_(o)
+
+    def set_expressions(self, exprs: Sequence[Tuple[np.ndarray, int]]):
+        torch = self.torch
+        with torch.cuda.device(self.dev):
+            self.words = [(torch.from_numpy(np.ascontiguousarray(ids[None])).to(self.dev), torch.full((1,), n, dtype=torch.int32).to(self.dev))
+                          for ids, n in exprs]
+
+    def _copy(self, levels, dst, src, nbytes, n, dst_idx, src_idx, dst_cap, src_cap, stream):
+        _lib.call("cmpc_taps_copy", levels, dst, src, nbytes, n, dst_idx, src_idx, dst_cap, src_cap, stream.cuda_stream)
+
+    def backbone(self, first: int, images: List[np.ndarray], n: int):
+        """Upload, cmpc_eval_prep and one backbone pass of the B frames `images` (frames first .. first + n - 1 and the pads of a short
+        last batch), then the taps of the n real frames into ring slots frame % ring; the batch's event behind them."""
+        torch, m, C = self.torch, self.model, self.C
+        descs, nbytes = plan_prep([a.shape for a in images], m.H, m.W)
+        main = torch.cuda.current_stream(self.dev)
+        bb = m.bb_stream if m.bb_stream is not None else main
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            with torch.cuda.stream(bb):
+                src = self.staging.upload(images, descs, nbytes)
+                _lib.call("cmpc_eval_prep", src.data_ptr(), nbytes, descs, len(images), m.H, m.W, self.proc.data_ptr(), self.feed.data_ptr(),
+                          bb.cuda_stream)
+            feats, _ = m.features_async(self.feed)         # the backbone stream waits for the caller's stream here
+            with torch.cuda.stream(bb):
+                for j in range(n):
+                    self._idx_a[j] = (first + j) % self.ring
+                src_p = (C.c_void_p * 3)(*[t.data_ptr() for t in feats])
+                self._copy(3, self._cache_p, src_p, self._bytes, n, self._idx_a, self._seq, self.ring, self.B, bb)
+                if self.dcrf:
+                    self._copy(1, (C.c_void_p * 1)(self.proc_ring.data_ptr()), (C.c_void_p * 1)(self.proc.data_ptr()), self._proc_bytes, n,
+                               self._idx_a, self._seq, self.ring, self.B, bb)
+                self.batch_ev[(first // self.B) % len(self.batch_ev)].record(bb)
+
+    def gather(self, f: int, idx: Sequence[int]):
+        """The cached taps of frames `idx` (sampled_frames(f)) into the head's inputs, once the newest batch among them is complete."""
+        torch = self.torch
+        main = torch.cuda.current_stream(self.dev)
+        with torch.cuda.device(self.dev):
+            main.wait_event(self.batch_ev[(max(idx) // self.B) % len(self.batch_ev)])
+            for j, g in enumerate(idx):
+                self._idx_b[j] = g % self.ring
+            self._copy(3, self._gath_p, self._cache_p, self._bytes, len(idx), self._seq, self._idx_b, self.B, self.ring, main)
+
+    def head(self, f: int, e: int, descs, slot: int):
+        """Head of expression e on the gathered taps of frame f; its mask into the device buffer at the offset of descs[e]."""
+        torch, m = self.torch, self.model
+        words, sl = self.words[e]
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            o = m.head_video(self.gathered, words, sl)
+            if self.dcrf:
+                from . import crf
+                sigm = o["sigm"].float().reshape(1, m.H, m.W)
+                k = f % self.ring
+                score, thr = crf.dense_crf_batch(sigm, self.proc_ring[k: k + 1], device=self.dev, method=self.dcrf_method), 0.5
+            else:
+                score, thr = o[self.score].float().reshape(1, m.H, m.W), self.threshold
+            dt = _lib.EVAL_F32 if score.dtype == torch.float32 else _lib.EVAL_U8
+            _lib.call("cmpc_eval_mask_out", score.data_ptr(), dt, 1, m.H, m.W, float(thr), self.C.byref(descs[e]), self.mask_dev.data_ptr(),
+                      self.mask_dev.numel(), self.value, torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def finish(self, f: int, slot: int, nbytes: int):
+        """Frame f's masks (every expression) into pinned slot `slot`, its event behind the copy."""
+        torch = self.torch
+        with torch.cuda.device(self.dev):
+            self.host[slot][:nbytes].copy_(self.mask_dev[:nbytes], non_blocking=True)
+            self.events[slot].record(torch.cuda.current_stream(self.dev))
+
+    def done(self, slot: int) -> bool:
+        return self.events[slot].query()
+
+    def wait(self, slot: int):
+        self.events[slot].synchronize()
+
+    def view(self, slot: int) -> np.ndarray:
+        return self.host[slot].numpy()
+
+
+class ClipSegmenter:
+    """The video model over a whole video: for every frame f and expression e what the video driver computes on f's clip
+    (trainval_video.py:214-226 on the 16 frames of clip_window(f)), with each frame through the backbone once.
+
+        seg = ClipSegmenter(model, vocab)
+        for e, f, mask in seg.run(frames, expressions):        # frame by frame in order, within a frame the expressions in order
+
+    frames: original-size uint8 arrays [h, w, 3] or [h, w], any iterable, read lazily (the video's length need not be known: frame f's
+    heads go out once frame f + 7 was read or the video ended).  expressions: sentences (needs `vocab`) or (END-padded ids [T], seq_len)
+    pairs -- the form head_video takes after model.video_words.  mask = value * (resize_and_crop(score >= threshold, *out_size(h, w)) > 0)
+    with score = "up" (default, threshold 1e-9: trainval_video.py:225-226) or "sigm"; with dcrf the same resampling of the DenseCRF
+    argmax on sigm and frame f's proc_im (trainval_video.py:227-240).
+
+    Frames pass the backbone in consecutive batches of len(FRAME_IDX) = 5 (a short last batch padded with its first frame); their taps
+    are kept in a ring of `ring` frames (slot = frame % ring) and each frame's clip is gathered from it by one cmpc_taps_copy.  A batch
+    is enqueued `lookahead` batches ahead of the first head that needs it and only when every frame it evicts is older than
+    f - frames // 2 for the oldest frame f whose heads are not all enqueued (min_ring).  depth: frames whose masks are in flight behind
+    the one being handed out (depth + 1 pinned slots); copy=False yields views of the pinned slot, valid until the next iteration.
+    stats after a run: {"frames": N, "backbone_passes": ceil(N / 5), "gathers": N, "heads": N * E}."""
+
+    def __init__(self, model, vocab=None, score: str = "up", threshold: float = 1e-9, out_size: Callable[[int, int], Tuple[int, int]] = full_size,
+                 value: int = 255, dcrf: bool = False, dcrf_method: str = "lattice", ring: int = 32, depth: int = 2, copy: bool = True,
+                 _stage=None, lookahead: Optional[int] = None):
+        from .model import FRAME_IDX
+        if not getattr(model, "video", False):
+            raise ValueError("ClipSegmenter: expects the video model (CMPC_video_mm_tgraph_allvec); use FrameSegmenter for the image models")
+        if score not in ("up", "sigm"):
+            raise ValueError("score must be 'up' or 'sigm', got %r" % (score,))
+        if value not in (1, 255):
+            raise ValueError("value must be 1 or 255, got %r" % (value,))
+        if int(depth) < 1:
+            raise ValueError("depth must be >= 1, got %r" % (depth,))
+        self.lookahead = CLIP_LOOKAHEAD if lookahead is None else int(lookahead)
+        if self.lookahead < 0:
+            raise ValueError("lookahead must be >= 0, got %r" % (lookahead,))
+        self.frames, self.B = int(model.frames), len(FRAME_IDX)
+        self.behind, self.ahead = _reach(self.frames)
+        need = min_ring(self.frames, self.lookahead)
+        if int(ring) < need:
+            raise ValueError("ring = %r is smaller than min_ring(%d, %d) = %d" % (ring, self.frames, self.lookahead, need))
+        self.model, self.vocab, self.score, self.threshold, self.out_size, self.value = model, vocab, score, float(threshold), out_size, int(value)
+        self.dcrf, self.dcrf_method = bool(dcrf), _check_dcrf_method(dcrf_method)
+        self.ring, self.depth, self.copy = int(ring), int(depth), bool(copy)
+        self.T, self.H, self.W = model.num_steps, model.H, model.W
+        self.nslots = self.depth + 1
+        self.stats = {"frames": 0, "backbone_passes": 0, "gathers": 0, "heads": 0}
+        self.stage = _stage if _stage is not None else _ClipStage(model, self.ring, self.nslots, self.score, self.threshold, self.value,
+                                                                  self.dcrf, self.dcrf_method)
+
+    def _frame(self, f: int, im) -> Tuple[np.ndarray, Tuple[int, int]]:
+        try:
+            a = _images_u8([np.asarray(im)])[0]
+        except ValueError as e:
+            raise ValueError("frame %d: %s" % (f, str(e).split(": ", 1)[-1])) from None
+        oh, ow = self.out_size(int(a.shape[0]), int(a.shape[1]))
+        if int(oh) < 1 or int(ow) < 1:
+            raise ValueError("frame %d: out_size(%d, %d) = (%d, %d) is empty" % (f, a.shape[0], a.shape[1], oh, ow))
+        return a, (int(oh), int(ow))
+
+    def run(self, frames: Iterable, expressions: Sequence) -> Iterator[Tuple[int, int, np.ndarray]]:
+        exprs = [check_expression(i, ex, self.vocab, self.T) for i, ex in enumerate(expressions)]
+        if not exprs:
+            raise ValueError("ClipSegmenter.run: no expressions")
+        if len(exprs) > MAX_BATCH:
+            raise ValueError("ClipSegmenter.run: %d expressions, at most %d per run" % (len(exprs), MAX_BATCH))
+        st, B, E = self.stage, self.B, len(exprs)
+        stats = self.stats = {"frames": 0, "backbone_passes": 0, "gathers": 0, "heads": 0}
+        free = deque(range(self.nslots))
+        pending = deque()                          # (slot, frame, descs) in enqueue order = yield order
+        sizes = deque()                            # out sizes of the frames read whose heads are not enqueued yet
+        it = iter(frames)
+        st.set_expressions(exprs)
+        read, ended, f = 0, False, 0               # frames handed to the backbone; the iterator ran out; oldest frame without its heads
+
+        def hand_out(block: bool):
+            while pending and (block or st.done(pending[0][0])):
+                slot, fr, descs = pending.popleft()
+                st.wait(slot)
+                host = st.view(slot)
+                for e, d in enumerate(descs):
+                    mk = host[d.offset: d.offset + d.h * d.w].reshape(d.h, d.w)
+                    yield e, fr, (mk.copy() if self.copy else mk)
+                free.append(slot)                  # only now: the caller has moved past the slot's last mask
+                block = False
+
+        def next_batch():
+            """Read up to B frames and enqueue their backbone pass; False once the video has ended."""
+            nonlocal read, ended
+            ims = []
+            while len(ims) < B:
+                im = next(it, it)
+                if im is it:
+                    ended = True
+                    break
+                a, size = self._frame(read + len(ims), im)
+                ims.append(a)
+                sizes.append(size)
+            if not ims:
+                return False
+            # ring safety: every frame this batch evicts is older than anything a head not yet enqueued reads (min_ring)
+            assert read + len(ims) - 1 - self.ring < f - self.behind, (read, f, self.ring)
+            st.backbone(read, ims + [ims[0]] * (B - len(ims)), len(ims))
+            read += len(ims)
+            stats["backbone_passes"] += 1
+            return True
+
+        while True:
+            # the batch that holds the newest frame of f's clip, and `lookahead` more
+            want = (f + self.ahead) // B * B + B * (self.lookahead + 1)
+            while not ended and read < want:
+                next_batch()
+            if read == 0:
+                raise ValueError("ClipSegmenter.run: no frames")
+            if f >= read:
+                break
+            # frame f + ahead was read, or the video ended and `read` is its length
+            idx = sampled_frames(f, read, self.frames)
+            descs, nbytes = plan_masks([sizes.popleft()] * E, self.H, self.W)
+            st.reserve(nbytes)
+            if not free:
+                yield from hand_out(True)
+            slot = free.popleft()
+            st.gather(f, idx)
+            stats["gathers"] += 1
+            for e in range(E):
+                st.head(f, e, descs, slot)
+                stats["heads"] += 1
+            st.finish(f, slot, nbytes)
+            pending.append((slot, f, descs))
+            f += 1
+            stats["frames"] = f
+            yield from hand_out(False)
+        while pending:
+            yield from hand_out(True)

@@ -578,6 +578,21 @@ int cmpc_eval_mask_iu(const void* map, int map_dt, int B, int H, int W, float th
 int cmpc_eval_mask_out(const void* map, int map_dt, int B, int H, int W, float thresh, const cmpc_eval_desc* descs_host,
                        unsigned char* mask_out, int64_t out_bytes, int value, void* stream);
 
+/* ---- Cached backbone taps of a video (segment.ClipSegmenter: CMPC_video_mm_tgraph_allvec over whole videos).  The video graph reads
+ *      5 frames of every 16-frame clip and consecutive frames' clips share them, so each frame's taps are computed once, kept in a ring
+ *      and gathered per clip.  One launch moves whole per-frame blocks of up to CMPC_TAPS_MAX_LEVELS levels: for l < levels, j < n
+ *          dst[l] + dst_idx[j] * bytes[l]  <-  src[l] + src_idx[j] * bytes[l]            (bytes[l] bytes each)
+ *      in both directions: backbone output [5, h, w, C] -> ring slots (src_idx 0..4), and ring slots -> the head's contiguous
+ *      [5, h, w, C] inputs (dst_idx 0..4).  dst / src / bytes: HOST arrays of `levels` device pointers / block sizes; dst_idx / src_idx:
+ *      HOST arrays of n frame indices; dst_frames / src_frames: the capacity of the two buffer sets in frames.  Everything is validated
+ *      before anything is launched and reaches the kernel by value: no address depends on device memory.  n in 1..CMPC_TAPS_MAX_FRAMES;
+ *      bytes[l] a positive multiple of 16 and the pointers 16-byte aligned (16-byte vector accesses); every index inside its capacity;
+ *      src indices may repeat (a clamped window repeats frames), dst indices may not; the two buffer sets must not overlap ---------- */
+#define CMPC_TAPS_MAX_LEVELS 3
+#define CMPC_TAPS_MAX_FRAMES 8
+int cmpc_taps_copy(int levels, void* const* dst_host, const void* const* src_host, const int64_t* bytes_host, int n,
+                   const int* dst_idx_host, const int* src_idx_host, int dst_frames, int src_frames, void* stream);
+
 /* ---- Training feed from raw samples (util/data_reader_refvos.py:27-46, build_batches.py:62-75): the image half is cmpc_eval_prep's
  *      kernel, the mask half cuts the object out of the annotation and resamples it.  One annotation descriptor per sample (HOST memory,
  *      validated before anything is launched, passed by value); B <= CMPC_EVAL_MAX_BATCH --------------------------------------------- */
