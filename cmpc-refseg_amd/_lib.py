@@ -252,6 +252,8 @@ SIGNATURES = {
     "cmpc_eval_mask_iu": [_P, _I, _I, _I, _I, _F, _P, _L, C.POINTER(EvalDesc), _P, _P, _P],
     "cmpc_eval_mask_out": [_P, _I, _I, _I, _I, _F, C.POINTER(EvalDesc), _P, _L, _I, _P],
     "cmpc_train_prep": [_P, _L, C.POINTER(EvalDesc), _P, _L, C.POINTER(TrainDesc), _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "cmpc_clip_prep": [_P, _L, C.POINTER(EvalDesc), _I, _P, _L, C.POINTER(TrainDesc), _I, _I, _I, _P, _P, _P, _P],
+    "cmpc_train_accuracy": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "cmpc_taps_copy": [_I, _PP, _PP, C.POINTER(_L), _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _P],
     "cmpc_launch_trace": [_I, _P],
     "cmpc_launch_trace_read": [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_L)],
@@ -266,8 +268,11 @@ COUNTS = {"cmpc_param_count": [_P], "cmpc_tap_count": [_P], "cmpc_grad_bucket_co
 _lib = None
 
 
-# op-level entry points younger than the oldest build still used as the `prev` side of an A/B run; nothing in the package calls them
-_AB_OPTIONAL = ("cmpc_convlstm_bwd_gates", "cmpc_convlstm_peephole_grad", "cmpc_train_prep")
+# op-level entry points younger than the oldest build still used as the `prev` side of an A/B run (CMPC_LIB_PATH): such a build loads
+# without them.  The benchmarked train step calls none of them.  cmpc_train_prep / cmpc_clip_prep (feed.py) and cmpc_train_accuracy
+# (evaluate.train_accuracy, accuracy=True) are called by the package: on a build that lacks them call() raises ctypes' AttributeError
+# (undefined symbol) at the first such call -- the feeders and accuracy=True need the in-tree library, and there is no other path.
+_AB_OPTIONAL = ("cmpc_convlstm_bwd_gates", "cmpc_convlstm_peephole_grad", "cmpc_train_prep", "cmpc_clip_prep", "cmpc_train_accuracy")
 
 
 def load():

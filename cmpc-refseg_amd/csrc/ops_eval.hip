@@ -587,6 +587,61 @@ extern "C" int cmpc_eval_mask_iu(const void* map, int map_dt, int B, int H, int 
     return cmpc_check_launch("eval_mask_iu");
 }
 
+namespace {
+
+// cmpc_train_prep's annotation half, validation: descriptors -> kernel arguments and the tile / LDS size.  Nothing is launched.
+int plan_target(const char* who, const unsigned char* ann, int64_t ann_bytes, const cmpc_train_desc* ann_descs_host, int B, int H, int W,
+                int order, TrainArgs& a, size_t& lds) {
+    if (order != 0 && order != 1) { cmpc_set_error("%s: order %d is neither 0 nor 1", who, order); return CMPC_EINVAL; }
+    if ((uintptr_t)ann & 3) { cmpc_set_error("%s: the annotation buffer is not 4-byte aligned", who); return CMPC_EINVAL; }
+    cmpc_eval_desc e[CMPC_EVAL_MAX_BATCH];
+    for (int b = 0; b < B; ++b) {
+        const cmpc_train_desc& d = ann_descs_host[b];
+        if (d.kind != CMPC_ANN_COLOR && d.kind != CMPC_ANN_PLAIN) { cmpc_set_error("%s: sample %d: unknown annotation kind %d", who, b, d.kind); return CMPC_EINVAL; }
+        if (d.kind == CMPC_ANN_COLOR ? (d.c != 3 && d.c != 4) : d.c != 1) {
+            cmpc_set_error("%s: sample %d: %d channels for a %s annotation", who, b, d.c, d.kind == CMPC_ANN_COLOR ? "colour-coded" : "plain");
+            return CMPC_EINVAL;
+        }
+        if (d.kind == CMPC_ANN_COLOR ? (d.match < 1 || d.match > 3) : d.match != 0) {
+            cmpc_set_error("%s: sample %d: %d channels to match (1..3 for a colour-coded annotation, 0 for a plain mask)", who, b, d.match);
+            return CMPC_EINVAL;
+        }
+        e[b] = cmpc_eval_desc{d.offset, d.h, d.w, 1, d.rh, d.rw, d.top, d.left, 0};
+        if (d.h > 0 && d.w > 0 && d.offset >= 0 && d.offset <= ann_bytes && (int64_t)d.h * d.w * d.c > ann_bytes - d.offset) {
+            cmpc_set_error("%s: sample %d: offset %lld + %lld bytes beyond the buffer (%lld)", who, b, (long long)d.offset,
+                           (long long)d.h * d.w * d.c, (long long)ann_bytes);
+            return CMPC_EINVAL;
+        }
+    }
+    const int rc = check_descs(who, e, B, ann_bytes, H, W, true, a.g);
+    if (rc) return rc;
+    if (order == 0)
+        for (int b = 0; b < B; ++b) { a.g[b].sy = a.g[b].sx = 0.0; a.g[b].ry = a.g[b].rx = 0; }       // nearest sample: no Gaussian
+    static const int shapes[][2] = {{8, 32}, {4, 32}, {2, 32}, {1, 32}, {1, 16}, {1, 8}, {1, 4}, {1, 1}};
+    int ty = 0, tx = 0;
+    lds = 0;
+    for (auto& s : shapes) {
+        lds = 0;
+        for (int b = 0; b < B; ++b) lds = std::max(lds, tile_lds_bytes(tile_lds(a.g[b], s[0], s[1], ann_descs_host[b].h, ann_descs_host[b].w)));
+        if (lds <= LDS_CAP) { ty = s[0]; tx = s[1]; break; }
+    }
+    if (!ty) { cmpc_set_error("%s: source footprint does not fit in LDS", who); return CMPC_EINVAL; }
+    a.ann = ann; a.ann_bytes = ann_bytes;
+    a.H = H; a.W = W; a.B = B; a.order = order; a.ty = ty; a.tx = tx;
+    for (int b = 0; b < B; ++b) a.d[b] = ann_descs_host[b];
+    return CMPC_OK;
+}
+
+// the planned annotations -> target_fine and pos: one memset and one train_target_kernel launch
+int launch_target(const char* who, TrainArgs& a, size_t lds, float* target_fine, uint64_t* pos, hipStream_t stream) {
+    a.target = target_fine; a.pos = (unsigned long long*)pos;
+    if (hipMemsetAsync(pos, 0, sizeof(uint64_t) * a.B, stream) != hipSuccess) { cmpc_set_error("%s: hipMemsetAsync", who); return CMPC_EHIP; }
+    hipLaunchKernelGGL(train_target_kernel, dim3((a.W + a.tx - 1) / a.tx, (a.H + a.ty - 1) / a.ty, a.B), dim3(NTHR), lds, stream, a);
+    return cmpc_check_launch(who);
+}
+
+}  // namespace
+
 extern "C" int cmpc_train_prep(const unsigned char* img, int64_t img_bytes, const cmpc_eval_desc* img_descs_host, const unsigned char* ann,
                                int64_t ann_bytes, const cmpc_train_desc* ann_descs_host, int B, int H, int W, int order,
                                unsigned char* proc_im, float* feed, float* target_fine, uint64_t* pos, void* stream) {
@@ -595,50 +650,31 @@ extern "C" int cmpc_train_prep(const unsigned char* img, int64_t img_bytes, cons
     if (images && (!img || !img_descs_host || !feed)) { cmpc_set_error("train_prep: NULL pointer (img, img_descs and feed go together)"); return CMPC_EINVAL; }
     if (B <= 0 || B > CMPC_EVAL_MAX_BATCH) { cmpc_set_error("train_prep: B = %d outside 1..%d", B, CMPC_EVAL_MAX_BATCH); return CMPC_EINVAL; }
     if (H <= 0 || W <= 0 || ann_bytes <= 0 || (images && img_bytes <= 0)) { cmpc_set_error("train_prep: bad output size %d x %d or buffer length", H, W); return CMPC_EINVAL; }
-    if (order != 0 && order != 1) { cmpc_set_error("train_prep: order %d is neither 0 nor 1", order); return CMPC_EINVAL; }
-    if ((uintptr_t)ann & 3) { cmpc_set_error("train_prep: the annotation buffer is not 4-byte aligned"); return CMPC_EINVAL; }
     TrainArgs a;
-    cmpc_eval_desc e[CMPC_EVAL_MAX_BATCH];
-    for (int b = 0; b < B; ++b) {
-        const cmpc_train_desc& d = ann_descs_host[b];
-        if (d.kind != CMPC_ANN_COLOR && d.kind != CMPC_ANN_PLAIN) { cmpc_set_error("train_prep: sample %d: unknown annotation kind %d", b, d.kind); return CMPC_EINVAL; }
-        if (d.kind == CMPC_ANN_COLOR ? (d.c != 3 && d.c != 4) : d.c != 1) {
-            cmpc_set_error("train_prep: sample %d: %d channels for a %s annotation", b, d.c, d.kind == CMPC_ANN_COLOR ? "colour-coded" : "plain");
-            return CMPC_EINVAL;
-        }
-        if (d.kind == CMPC_ANN_COLOR ? (d.match < 1 || d.match > 3) : d.match != 0) {
-            cmpc_set_error("train_prep: sample %d: %d channels to match (1..3 for a colour-coded annotation, 0 for a plain mask)", b, d.match);
-            return CMPC_EINVAL;
-        }
-        e[b] = cmpc_eval_desc{d.offset, d.h, d.w, 1, d.rh, d.rw, d.top, d.left, 0};
-        if (d.h > 0 && d.w > 0 && d.offset >= 0 && d.offset <= ann_bytes && (int64_t)d.h * d.w * d.c > ann_bytes - d.offset) {
-            cmpc_set_error("train_prep: sample %d: offset %lld + %lld bytes beyond the buffer (%lld)", b, (long long)d.offset,
-                           (long long)d.h * d.w * d.c, (long long)ann_bytes);
-            return CMPC_EINVAL;
-        }
-    }
-    int rc = check_descs("train_prep", e, B, ann_bytes, H, W, true, a.g);
+    size_t lds = 0;
+    int rc = plan_target("train_prep", ann, ann_bytes, ann_descs_host, B, H, W, order, a, lds);
     if (rc) return rc;
-    if (order == 0)
-        for (int b = 0; b < B; ++b) { a.g[b].sy = a.g[b].sx = 0.0; a.g[b].ry = a.g[b].rx = 0; }       // nearest sample: no Gaussian
-    static const int shapes[][2] = {{8, 32}, {4, 32}, {2, 32}, {1, 32}, {1, 16}, {1, 8}, {1, 4}, {1, 1}};
-    size_t lds = 0; int ty = 0, tx = 0;
-    for (auto& s : shapes) {
-        lds = 0;
-        for (int b = 0; b < B; ++b) lds = std::max(lds, tile_lds_bytes(tile_lds(a.g[b], s[0], s[1], ann_descs_host[b].h, ann_descs_host[b].w)));
-        if (lds <= LDS_CAP) { ty = s[0]; tx = s[1]; break; }
-    }
-    if (!ty) { cmpc_set_error("train_prep: source footprint does not fit in LDS"); return CMPC_EINVAL; }
     if (images) {
         rc = launch_prep("train_prep", img, img_bytes, img_descs_host, B, H, W, proc_im, feed, ST);
         if (rc) return rc;
     }
-    a.ann = ann; a.ann_bytes = ann_bytes; a.target = target_fine; a.pos = (unsigned long long*)pos;
-    a.H = H; a.W = W; a.B = B; a.order = order; a.ty = ty; a.tx = tx;
-    for (int b = 0; b < B; ++b) a.d[b] = ann_descs_host[b];
-    if (hipMemsetAsync(pos, 0, sizeof(uint64_t) * B, ST) != hipSuccess) { cmpc_set_error("train_prep: hipMemsetAsync"); return CMPC_EHIP; }
-    hipLaunchKernelGGL(train_target_kernel, dim3((W + tx - 1) / tx, (H + ty - 1) / ty, B), dim3(NTHR), lds, ST, a);
-    return cmpc_check_launch("train_prep");
+    return launch_target("train_prep", a, lds, target_fine, pos, ST);
+}
+
+// One clip of the video model: n_img frames through cmpc_eval_prep's kernel and the key frame's annotation through cmpc_train_prep's
+extern "C" int cmpc_clip_prep(const unsigned char* img, int64_t img_bytes, const cmpc_eval_desc* img_descs_host, int n_img,
+                              const unsigned char* ann, int64_t ann_bytes, const cmpc_train_desc* ann_desc_host, int H, int W, int order,
+                              float* feed, float* target_fine, uint64_t* pos, void* stream) {
+    if (!img || !img_descs_host || !ann || !ann_desc_host || !feed || !target_fine || !pos) { cmpc_set_error("clip_prep: NULL pointer"); return CMPC_EINVAL; }
+    if (n_img <= 0 || n_img > CMPC_TAPS_MAX_FRAMES) { cmpc_set_error("clip_prep: n_img = %d outside 1..%d", n_img, CMPC_TAPS_MAX_FRAMES); return CMPC_EINVAL; }
+    if (H <= 0 || W <= 0 || ann_bytes <= 0 || img_bytes <= 0) { cmpc_set_error("clip_prep: bad output size %d x %d or buffer length", H, W); return CMPC_EINVAL; }
+    TrainArgs a;
+    size_t lds = 0;
+    int rc = plan_target("clip_prep", ann, ann_bytes, ann_desc_host, 1, H, W, order, a, lds);
+    if (rc) return rc;
+    rc = launch_prep("clip_prep", img, img_bytes, img_descs_host, n_img, H, W, nullptr, feed, ST);
+    if (rc) return rc;
+    return launch_target("clip_prep", a, lds, target_fine, pos, ST);
 }
 
 extern "C" int cmpc_eval_mask_out(const void* map, int map_dt, int B, int H, int W, float thresh, const cmpc_eval_desc* descs_host,

@@ -217,6 +217,37 @@ def masks_out(score_map, sizes: Sequence[Tuple[int, int]], thresh: float = 1e-9,
     return buf, descs
 
 
+def train_accuracy(pred, target_fine, out: torch.Tensor = None) -> torch.Tensor:
+    """Per sample (n_pos, n_neg, correct_pos, correct_neg) of compute_accuracy(pred[b], resize_bilinear(target_fine, pred's size)[b])
+    (util/processing_tools.py:24-35 on model.pred / model.target) on the device: one cmpc_train_accuracy launch on the current stream,
+    nothing synchronises.  pred: float32 device tensor [B, h, w] or [B, h, w, 1]; target_fine: float32 [B, H, W] or [B, H, W, 1] on
+    the same device, h <= H, w <= W.  Returns an int64 device tensor [B, 4] (`out` when given); hostutil.accuracy_from_counts turns it
+    into the three fractions."""
+    ts = []
+    for name, t in (("pred", pred), ("target_fine", target_fine)):
+        if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != torch.float32:
+            raise ValueError("%s must be a float32 device tensor" % name)
+        if t.dim() == 4 and t.shape[3] == 1:
+            t = t[..., 0]
+        if t.dim() != 3:
+            raise ValueError("%s must be [B, h, w] or [B, h, w, 1], got %s" % (name, tuple(t.shape)))
+        ts.append(t.contiguous())
+    p, f = ts
+    if p.device != f.device or p.shape[0] != f.shape[0]:
+        raise ValueError("pred %s on %s and target_fine %s on %s: one device and one batch size" % (tuple(p.shape), p.device, tuple(f.shape), f.device))
+    B, h, w = p.shape
+    H, W = f.shape[1:]
+    if B > MAX_BATCH or h > H or w > W:
+        raise ValueError("pred [%d, %d, %d] against target_fine [%d, %d]: at most %d samples, and pred no larger than the target" % (B, h, w, H, W, MAX_BATCH))
+    dev = p.device
+    with torch.cuda.device(dev):
+        counts = out if out is not None else torch.empty(B, 4, dtype=torch.int64, device=dev)
+        if tuple(counts.shape) != (B, 4) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.device != dev:
+            raise ValueError("out must be a contiguous int64 [B, 4] tensor on %s" % dev)
+        _lib.call("cmpc_train_accuracy", p.data_ptr(), f.data_ptr(), B, h, w, H, W, counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return counts
+
+
 def unpack_masks(buf, descs) -> list:
     """The [h, w] views of a packed mask buffer (device tensor or NumPy array) at its descriptors' offsets."""
     if torch.is_tensor(buf):

@@ -3,10 +3,14 @@ with the resampling on the GPU and the host work off the train step's critical p
 
     feed, target_fine, pos = prepare_batch(images, annotations, keys, H, W)      # one cmpc_train_prep call, current stream
     target_fine, pos = prepare_targets(annotations, keys, H, W)                   # the mask half alone
+    frames, target_fine, pos = prepare_clip(frames5, annotation, key, H, W)       # one clip of the video model: one cmpc_clip_prep call
 
     feeder = TrainFeeder(model, samples, vocab=vocab)        # samples[i] -> (image, annotation, key_or_None, text)
     for _ in range(iters):
         step, scalars = feeder.step()                        # model.train_step on the staged batch (lookahead=True: next batch as next_im)
+
+    feeder = ClipTrainFeeder(video_model, clips, vocab=vocab)   # clips[i] -> (frames, annotation, key_or_None, text)
+    step, scalars = feeder.step(accuracy=True)                  # model.train_step_video_frames on the staged clip (one cmpc_clip_prep call)
 
 A sample is an original-size uint8 image ([h, w, 3] or [h, w]), an annotation at the same size -- colour-coded uint8 [h, w, 3|4] with
 a key colour (REFVOS_OBJECT_COLOR), or with key None a plain mask [h, w], non-zero = object -- and a sentence.  Decoding files is the
@@ -174,6 +178,34 @@ def prepare_batch(images, annotations, keys, H: int, W: int, order: int = 1, mat
     return _prep(list(images), list(annotations), keys, H, W, order, match, device)
 
 
+def prepare_clip(frames, annotation, key, H: int, W: int, order: int = 1, match: int = 1, device="cuda:0"):
+    """(frames float32 [n, H, W, 3], target_fine float32 [1, H, W, 1], pos int64 [1]) of one clip of the video model from one
+    cmpc_clip_prep call on the current stream: evaluate.prepare_images' feed of the n (<= 8) sampled frames -- original-size uint8, all
+    one size -- and prepare_targets of the key frame's annotation, bit for bit.  Nothing synchronises."""
+    import torch
+    from .evaluate import _staging
+    _check_order(order)
+    ims = _images_u8(list(frames))
+    if not 1 <= len(ims) <= _lib.TAPS_MAX_FRAMES:
+        raise ValueError("%d frames: expected 1..%d (the clip's sampled frames)" % (len(ims), _lib.TAPS_MAX_FRAMES))
+    ann, kind, k = annotation_u8(annotation, key)
+    for i, im in enumerate(ims):
+        if im.shape != ims[0].shape or im.shape[:2] != ann.shape[:2]:
+            raise ValueError("frame %d is %s, frame 0 %s, the annotation %s (one size for all)" % (i, im.shape, ims[0].shape, ann.shape[:2]))
+    idesc, ibytes = plan_images([a.shape for a in ims], H, W)
+    adesc, abytes = plan_targets([ann.shape], [kind], [k], H, W, match)
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        isrc = _staging(dev, "im").upload(ims, idesc, ibytes)
+        asrc = _staging(dev, "ann").upload([ann], adesc, abytes)
+        feed = torch.empty(len(ims), H, W, 3, dtype=torch.float32, device=dev)
+        target = torch.empty(1, H, W, 1, dtype=torch.float32, device=dev)
+        pos = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.call("cmpc_clip_prep", isrc.data_ptr(), ibytes, idesc, len(ims), asrc.data_ptr(), abytes, adesc, H, W, order,
+                  feed.data_ptr(), target.data_ptr(), pos.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return feed, target, pos
+
+
 class EpochSampler:
     """An endless stream of sample indices like run_prefetch's (data_reader_refvos.py:48-72): a fresh permutation every epoch, seeded
     (default_rng([seed, epoch])) so that a run can be repeated.  With world > 1 every rank takes perm[rank::world] cut to n // world
@@ -253,7 +285,7 @@ class HostPipeline:
         self.buffers, self.max_pixels, self.skip_empty = buffers, int(max_pixels), bool(skip_empty)
         self.words_bytes = _align(B * T * 4)
         self.img_off = self.words_bytes + _align(B * 4)
-        self.capacity = slot_capacity(B, T, max_pixels)
+        self.capacity = self._capacity()
         for b in buffers:
             if b.dtype != np.uint8 or b.ndim != 1 or b.shape[0] < self.capacity:
                 raise ValueError("a slot buffer must be uint8 [>= %d]" % self.capacity)
@@ -267,6 +299,9 @@ class HostPipeline:
         self._window = 2 * B                         # samples loading ahead of the packer
         self._thread = threading.Thread(target=self._run, name="cmpc-feed-pack", daemon=True)
         self._thread.start()
+
+    def _capacity(self) -> int:
+        return slot_capacity(self.B, self.T, self.max_pixels)
 
     # -- loader pool ------------------------------------------------------------------------------------------------------------------
     def _load(self, index: int) -> _Sample:
@@ -358,12 +393,75 @@ def slot_capacity(B: int, T: int, max_pixels: int) -> int:
     return _align(B * T * 4) + _align(B * 4) + B * (_align(max_pixels * 3) + _align(max_pixels * 4))
 
 
+def clip_slot_capacity(T: int, n_img: int, max_pixels: int) -> int:
+    """Bytes of one ring slot of the clip feed: words, seq_len, n_img frames of up to max_pixels x 3 and one annotation of up to
+    max_pixels x 4."""
+    return _align(T * 4) + _align(4) + n_img * _align(max_pixels * 3) + _align(max_pixels * 4)
+
+
+class ClipPipeline(HostPipeline):
+    """HostPipeline for the video model: a batch is ONE clip -- words ‖ seq_len ‖ the frames at positions `frame_idx` ‖ the annotation.
+    samples[i] -> (frames, annotation, key_or_None, text); only frames[j] for j in frame_idx is ever indexed, so a lazy sequence
+    decodes those files alone."""
+
+    def __init__(self, samples, sampler, vocab, T, H, W, buffers, max_pixels, frame_idx, n_frames, skip_empty=False, match=1, workers=WORKERS):
+        self.frame_idx, self.n_frames = tuple(int(j) for j in frame_idx), int(n_frames)
+        super().__init__(samples, sampler, vocab, 1, T, H, W, buffers, max_pixels, skip_empty=skip_empty, match=match, workers=workers)
+
+    def _capacity(self) -> int:
+        return clip_slot_capacity(self.T, len(self.frame_idx), self.max_pixels)
+
+    def _load(self, index: int) -> _Sample:
+        frames, annotation, key, text = self.samples[index]
+        if hasattr(frames, "__len__") and len(frames) != self.n_frames:
+            raise ValueError("sample %d: %d frames, the model's clips hold %d" % (index, len(frames), self.n_frames))
+        s = _Sample()
+        s.index = index
+        try:
+            s.image = _images_u8([frames[j] for j in self.frame_idx])
+        except ValueError as e:
+            raise ValueError("sample %d: %s" % (index, e)) from None
+        shape = s.image[0].shape
+        for j, f in zip(self.frame_idx, s.image):
+            if f.shape != shape:
+                raise ValueError("sample %d: frame %d is %s, frame %d is %s (a clip's frames are all one size)" % (index, j, f.shape, self.frame_idx[0], shape))
+        s.ann, s.kind, s.key = annotation_u8(annotation, key, index)
+        if shape[:2] != s.ann.shape[:2]:
+            raise ValueError("sample %d: frames %s, annotation %s (the annotation is at the frames' size)" % (index, shape[:2], s.ann.shape[:2]))
+        if shape[0] * shape[1] > self.max_pixels:
+            raise ValueError("sample %d: %d x %d pixels exceed the ring's slots (ClipTrainFeeder(max_hw=...) sizes them)" % (index, shape[0], shape[1]))
+        s.ids, s.seq_len = encode_text(text, self.vocab, self.T)
+        s.text = text if isinstance(text, str) else None
+        s.empty = self.skip_empty and not HU.object_mask(annotation, key, self.match).any()
+        return s
+
+    def _pack(self, slot: int, batch: List[_Sample]) -> HostBatch:
+        s, T = batch[0], self.T
+        buf = self.buffers[slot]
+        hb = HostBatch()
+        hb.slot = slot
+        buf[: T * 4].view(np.int32)[...] = s.ids
+        buf[self.words_bytes: self.words_bytes + 4].view(np.int32)[...] = s.seq_len
+        hb.img_descs, hb.img_bytes = plan_images([f.shape for f in s.image], self.H, self.W)
+        hb.ann_descs, hb.ann_bytes = plan_targets([s.ann.shape], [s.kind], [s.key], self.H, self.W, self.match)
+        hb.img_off, hb.ann_off = self.img_off, self.img_off + hb.img_bytes
+        hb.nbytes = hb.ann_off + hb.ann_bytes
+        for f, di in zip(s.image, hb.img_descs):
+            o = hb.img_off + di.offset
+            buf[o: o + f.size] = f.reshape(-1)
+        o = hb.ann_off + hb.ann_descs[0].offset
+        buf[o: o + s.ann.size] = s.ann.reshape(-1)
+        hb.indices = [s.index]
+        hb.sentences = [s.text]
+        return hb
+
+
 class _DeviceStage:
     """The feed's device half, run by the caller's thread only: per slot a pinned host buffer, its device twin and the outputs, all
     allocated here once.  stage() enqueues one copy and one cmpc_train_prep call on the side stream behind the event of the slot's last
     reader; release() records that event."""
 
-    def __init__(self, model, nslots: int, capacity: int, order: int):
+    def __init__(self, model, nslots: int, capacity: int, order: int, n_img: Optional[int] = None):
         import torch
         self.torch = torch
         self.model, self.order = model, order
@@ -377,7 +475,7 @@ class _DeviceStage:
             self.raw = [torch.empty(capacity, dtype=torch.uint8, device=self.dev) for _ in range(nslots)]
             self.words = [r[: B * T * 4].view(torch.int32).view(B, T) for r in self.raw]
             self.seq_len = [r[wb: wb + B * 4].view(torch.int32) for r in self.raw]
-            self.im = [torch.empty(B, H, W, 3, dtype=torch.float32, device=self.dev) for _ in range(nslots)]
+            self.im = [torch.empty(B if n_img is None else n_img, H, W, 3, dtype=torch.float32, device=self.dev) for _ in range(nslots)]
             self.target = [torch.empty(B, H, W, 1, dtype=torch.float32, device=self.dev) for _ in range(nslots)]
             self.pos = [torch.zeros(B, dtype=torch.int64, device=self.dev) for _ in range(nslots)]
             # every event exists before the first step (the backbone's graph capture must see no new HIP object from here)
@@ -399,13 +497,16 @@ class _DeviceStage:
             with torch.cuda.stream(fs):
                 raw[: hb.nbytes].copy_(self.host[k][: hb.nbytes], non_blocking=True)
                 self.copied[k].record(fs)
-                base = raw.data_ptr()
-                _lib.call("cmpc_train_prep", base + hb.img_off, hb.img_bytes, hb.img_descs, base + hb.ann_off, hb.ann_bytes, hb.ann_descs,
-                          self.B, self.H, self.W, self.order, None, self.im[k].data_ptr(), self.target[k].data_ptr(), self.pos[k].data_ptr(),
-                          fs.cuda_stream)
+                self._prep(hb, k, raw.data_ptr(), fs.cuda_stream)
                 self.ready[k].record(fs)
-        return {"words": self.words[k], "im": self.im[k], "target_fine": self.target[k], "seq_len": self.seq_len[k], "pos": self.pos[k],
+        return {"words": self.words[k], self.IM_KEY: self.im[k], "target_fine": self.target[k], "seq_len": self.seq_len[k], "pos": self.pos[k],
                 "ready": self.ready[k], "indices": hb.indices, "sentences": hb.sentences, "skipped": hb.skipped, "slot": k}
+
+    IM_KEY = "im"
+
+    def _prep(self, hb: HostBatch, k: int, base: int, st: int):
+        _lib.call("cmpc_train_prep", base + hb.img_off, hb.img_bytes, hb.img_descs, base + hb.ann_off, hb.ann_bytes, hb.ann_descs,
+                  self.B, self.H, self.W, self.order, None, self.im[k].data_ptr(), self.target[k].data_ptr(), self.pos[k].data_ptr(), st)
 
     def wait_ready(self, feed: Dict):
         """Order the current stream behind the batch (words, seq_len and target_fine are read there; the backbone waits for `ready` itself)."""
@@ -421,41 +522,23 @@ class _DeviceStage:
         self.torch.cuda.synchronize(self.dev)
 
 
-class TrainFeeder:
-    """Raw samples -> device-resident train feeds, prepared on a side stream while the previous step runs.
+class _ClipStage(_DeviceStage):
+    """_DeviceStage for the video model: the slot's images are the clip's sampled frames, prepared by one cmpc_clip_prep call."""
+    IM_KEY = "frames"
 
-    samples[i] returns (image, annotation, key_or_None, text); `sampler` yields indices endlessly (default EpochSampler(len(samples)));
-    text is a sentence (needs `vocab`, hostutil.load_vocab_dict_from_file), an (ids, seq_len) pair, or a front-padded id row.  B, T, H, W
-    are the model's.  Iterating yields feeds: dicts of `words` int32 [B, T], `im` float32 [B, H, W, 3], `target_fine` float32 [B, H, W, 1],
-    `seq_len` int32 [B], `pos` int64 [B] (foreground pixels of each target: 0 = the object is absent), all device tensors of the ring,
-    `ready` (the event recorded once they are complete), and the host-side `indices` and `sentences`.  A feed's tensors stay valid for
-    work enqueued on the current stream until the next feed is requested.  step() runs model.train_step on the next feed, its backbone
-    waiting for `ready` alone; with lookahead=True it also hands over the look-ahead batch as `next_im`, so that batch's backbone pass
-    is enqueued where train_step's docstring says.  Bit-identical either way; the default is the faster one (DESIGN.md 13d: the
-    look-ahead placement costs the step 9 % with resident feeds already, as bench.py --prefetch shows).
+    def __init__(self, model, nslots: int, capacity: int, order: int):
+        super().__init__(model, nslots, capacity, order, n_img=len(model.FRAME_IDX))
 
-    depth: batches staged ahead of the one in use; the ring holds depth + model.MAX_STEPS_IN_FLIGHT slots, each sized for B samples of
-    up to max_hw pixels (a larger sample raises ValueError).  skip_empty drops samples whose object is absent at the original size
-    (counted in `skipped`); by default they are kept, their target all zero and pos 0.  close() stops the threads."""
+    def _prep(self, hb: HostBatch, k: int, base: int, st: int):
+        _lib.call("cmpc_clip_prep", base + hb.img_off, hb.img_bytes, hb.img_descs, len(hb.img_descs), base + hb.ann_off, hb.ann_bytes,
+                  hb.ann_descs, self.H, self.W, self.order, self.im[k].data_ptr(), self.target[k].data_ptr(), self.pos[k].data_ptr(), st)
 
-    def __init__(self, model, samples, sampler=None, vocab=None, order: int = 1, depth: int = 2, skip_empty: bool = False, match: int = 1,
-                 max_hw: Tuple[int, int] = (720, 1280), workers: int = WORKERS, lookahead: bool = False, _stage=None):
-        if getattr(model, "video", False):
-            raise ValueError("TrainFeeder: the video model (CMPC_video_mm_tgraph_allvec) is not supported; its batches are built offline at the input size")
-        _check_order(order)
-        if depth < 1:
-            raise ValueError("depth must be >= 1 (the look-ahead batch), got %d" % depth)
-        self.model, self.order, self.depth, self.lookahead = model, order, depth, bool(lookahead)
-        self.B, self.T, self.H, self.W = model.batch_size, model.num_steps, model.H, model.W
-        if self.B > MAX_BATCH:
-            raise ValueError("TrainFeeder: model.batch_size %d > %d" % (self.B, MAX_BATCH))
-        max_pixels = int(max_hw[0]) * int(max_hw[1])
-        nslots = depth + int(getattr(model, "MAX_STEPS_IN_FLIGHT", 2))
-        self.stage = _stage if _stage is not None else _DeviceStage(model, nslots, slot_capacity(self.B, self.T, max_pixels), order)
-        if sampler is None:
-            sampler = EpochSampler(len(samples))
-        self.pipe = HostPipeline(samples, sampler, vocab, self.B, self.T, self.H, self.W, self.stage.buffers(), max_pixels,
-                                 skip_empty=skip_empty, match=match, workers=workers)
+
+class _RingFeeder:
+    """What TrainFeeder and ClipTrainFeeder share: feeds staged ahead through `self.stage` / `self.pipe`, handed out one at a time."""
+
+    def _start(self, depth: int):
+        self.depth = depth
         self._staged = deque()                       # feeds staged and not handed out yet
         self._current = None                         # the feed handed out last (released when the next one is requested)
         self._copying: List[int] = []                # released slots whose pinned bytes may still be in flight
@@ -512,18 +595,6 @@ class TrainFeeder:
         self._fill(1)
         return self._staged[0]
 
-    def step(self):
-        """One model.train_step on the next feed; returns train_step's result.  With lookahead the staged batch behind it goes along as
-        next_im / next_ready, and the following call passes the very tensor it showed there, so train_step finds its taps ready."""
-        feed = next(self)
-        nxt = self.peek()
-        self.stage.wait_ready(feed)
-        self.last_feed = feed
-        if not self.lookahead:                       # the batches are staged ahead all the same; each backbone pass starts with its own step
-            return self.model.train_step(feed["words"], feed["im"], feed["target_fine"], feed["seq_len"], ready=feed["ready"])
-        return self.model.train_step(feed["words"], feed["im"], feed["target_fine"], feed["seq_len"], ready=feed["ready"],
-                                     next_im=nxt["im"], next_ready=nxt["ready"])
-
     def close(self):
         if self._closed:
             return
@@ -542,3 +613,102 @@ class TrainFeeder:
             self.close()
         except Exception:
             pass
+
+
+class TrainFeeder(_RingFeeder):
+    """Raw samples -> device-resident train feeds, prepared on a side stream while the previous step runs.
+
+    samples[i] returns (image, annotation, key_or_None, text); `sampler` yields indices endlessly (default EpochSampler(len(samples)));
+    text is a sentence (needs `vocab`, hostutil.load_vocab_dict_from_file), an (ids, seq_len) pair, or a front-padded id row.  B, T, H, W
+    are the model's.  Iterating yields feeds: dicts of `words` int32 [B, T], `im` float32 [B, H, W, 3], `target_fine` float32 [B, H, W, 1],
+    `seq_len` int32 [B], `pos` int64 [B] (foreground pixels of each target: 0 = the object is absent), all device tensors of the ring,
+    `ready` (the event recorded once they are complete), and the host-side `indices` and `sentences`.  A feed's tensors stay valid for
+    work enqueued on the current stream until the next feed is requested.  step() runs model.train_step on the next feed, its backbone
+    waiting for `ready` alone; with lookahead=True it also hands over the look-ahead batch as `next_im`, so that batch's backbone pass
+    is enqueued where train_step's docstring says.  Bit-identical either way; the default is the faster one (DESIGN.md 13d: the
+    look-ahead placement costs the step 9 % with resident feeds already, as bench.py --prefetch shows).
+
+    depth: batches staged ahead of the one in use; the ring holds depth + model.MAX_STEPS_IN_FLIGHT slots, each sized for B samples of
+    up to max_hw pixels (a larger sample raises ValueError).  skip_empty drops samples whose object is absent at the original size
+    (counted in `skipped`); by default they are kept, their target all zero and pos 0.  close() stops the threads."""
+
+    def __init__(self, model, samples, sampler=None, vocab=None, order: int = 1, depth: int = 2, skip_empty: bool = False, match: int = 1,
+                 max_hw: Tuple[int, int] = (720, 1280), workers: int = WORKERS, lookahead: bool = False, _stage=None):
+        if getattr(model, "video", False):
+            raise ValueError("TrainFeeder: the video model (CMPC_video_mm_tgraph_allvec) is not supported here: ClipTrainFeeder feeds it from raw clips")
+        _check_order(order)
+        if depth < 1:
+            raise ValueError("depth must be >= 1 (the look-ahead batch), got %d" % depth)
+        self.model, self.order, self.lookahead = model, order, bool(lookahead)
+        self.B, self.T, self.H, self.W = model.batch_size, model.num_steps, model.H, model.W
+        if self.B > MAX_BATCH:
+            raise ValueError("TrainFeeder: model.batch_size %d > %d" % (self.B, MAX_BATCH))
+        max_pixels = int(max_hw[0]) * int(max_hw[1])
+        nslots = depth + int(getattr(model, "MAX_STEPS_IN_FLIGHT", 2))
+        self.stage = _stage if _stage is not None else _DeviceStage(model, nslots, slot_capacity(self.B, self.T, max_pixels), order)
+        if sampler is None:
+            sampler = EpochSampler(len(samples))
+        self.pipe = HostPipeline(samples, sampler, vocab, self.B, self.T, self.H, self.W, self.stage.buffers(), max_pixels,
+                                 skip_empty=skip_empty, match=match, workers=workers)
+        self._start(depth)
+
+    def step(self):
+        """One model.train_step on the next feed; returns train_step's result.  With lookahead the staged batch behind it goes along as
+        next_im / next_ready, and the following call passes the very tensor it showed there, so train_step finds its taps ready."""
+        feed = next(self)
+        nxt = self.peek()
+        self.stage.wait_ready(feed)
+        self.last_feed = feed
+        if not self.lookahead:                       # the batches are staged ahead all the same; each backbone pass starts with its own step
+            return self.model.train_step(feed["words"], feed["im"], feed["target_fine"], feed["seq_len"], ready=feed["ready"])
+        return self.model.train_step(feed["words"], feed["im"], feed["target_fine"], feed["seq_len"], ready=feed["ready"],
+                                     next_im=nxt["im"], next_ready=nxt["ready"])
+
+
+class ClipTrainFeeder(_RingFeeder):
+    """Raw clips -> device-resident train feeds of the video model (CMPC_video_mm_tgraph_allvec), TrainFeeder's machinery per clip.
+
+    samples[i] returns (frames, annotation, key_or_None, text).  frames: a sequence of model.frames items or an array [frames, h, w, 3];
+    only positions model.FRAME_IDX are indexed (a lazy sequence decodes 5 files, not 16); those frames are uint8 [h, w, 3] or [h, w], all
+    one size.  annotation: at that size, colour-coded with a key colour or (key None) a plain mask, bool accepted; it belongs to clip
+    position frames // 2.  text as for TrainFeeder.  A stored train sample of build_A2D_batches.py:137-143 is
+    (z["frames"], z["mask_batch"], None, z["text_batch"]): already at H x W, the identity geometry.
+
+    Feeds are dicts of `words` int32 [1, T] (END-padded), `seq_len` int32 [1], `frames` float32 [5, H, W, 3] (BGR - mu),
+    `target_fine` float32 [1, H, W, 1], `pos` int64 [1], device tensors of the ring, plus `ready`, `indices`, `sentences`, `skipped`,
+    `slot`.  Per clip the caller's thread issues one host-to-device copy and one cmpc_clip_prep call on the feeder's side stream; a slot
+    is reused only behind the event recorded after the step that read it; nothing is allocated or synchronised in the steady state.
+    step(accuracy=False) runs model.train_step_video_frames on the next feed, its backbone waiting for `ready` alone.  There is no
+    look-ahead backbone pass: the video step has no next_im.  sampler, order, depth, skip_empty, match, max_hw, workers, peek(), close()
+    and the context manager behave as in TrainFeeder."""
+
+    def __init__(self, model, samples, sampler=None, vocab=None, order: int = 1, depth: int = 2, skip_empty: bool = False, match: int = 1,
+                 max_hw: Tuple[int, int] = (720, 1280), workers: int = WORKERS, _stage=None):
+        if not getattr(model, "video", False):
+            raise ValueError("ClipTrainFeeder feeds the video model (CMPC_video_mm_tgraph_allvec); TrainFeeder feeds the image models")
+        _check_order(order)
+        if depth < 1:
+            raise ValueError("depth must be >= 1 (the clip staged behind the one in use), got %d" % depth)
+        self.model, self.order = model, order
+        self.T, self.H, self.W = model.num_steps, model.H, model.W
+        frame_idx = tuple(model.FRAME_IDX)
+        if len(frame_idx) > _lib.TAPS_MAX_FRAMES:
+            raise ValueError("ClipTrainFeeder: %d sampled frames > %d" % (len(frame_idx), _lib.TAPS_MAX_FRAMES))
+        max_pixels = int(max_hw[0]) * int(max_hw[1])
+        nslots = depth + int(getattr(model, "MAX_STEPS_IN_FLIGHT", 2))
+        self.stage = _stage if _stage is not None else _ClipStage(model, nslots, clip_slot_capacity(self.T, len(frame_idx), max_pixels), order)
+        if sampler is None:
+            sampler = EpochSampler(len(samples))
+        self.pipe = ClipPipeline(samples, sampler, vocab, self.T, self.H, self.W, self.stage.buffers(), max_pixels, frame_idx, model.frames,
+                                 skip_empty=skip_empty, match=match, workers=workers)
+        self._start(depth)
+
+    def step(self, accuracy: bool = False):
+        """One model.train_step_video_frames on the next feed; returns its result.  The clip behind it is staged first, so its copy and
+        prep run beside this step."""
+        feed = next(self)
+        self.peek()
+        self.stage.wait_ready(feed)
+        self.last_feed = feed
+        return self.model.train_step_video_frames(feed["words"], feed["seq_len"], feed["frames"], feed["target_fine"], ready=feed["ready"],
+                                                  accuracy=accuracy)

@@ -253,3 +253,88 @@ def train_sample(image, annotation, key, H: int, W: int, order: int = 1, match: 
     obj = object_mask(annotation, key, match)
     tgt = resize_and_pad(obj, H, W) > 0 if order == 1 else resize_and_pad_order0(obj, H, W)
     return feed, tgt.astype(np.float32)[..., None]
+
+
+# ---- the train loops' accuracy lines (test.py:94-127, CMPC_video/trainval_video.py:93-123) ---------------------------------------------
+def accuracy_counts(scores, labels) -> np.ndarray:
+    """int64 [4] = (n_pos, n_neg, correct_pos, correct_neg): the integer sums compute_accuracy divides (what cmpc_train_accuracy
+    returns per sample)."""
+    s, l = np.asarray(scores), np.asarray(labels)
+    if s.shape != l.shape:
+        raise ValueError("scores %s and labels %s differ in shape" % (s.shape, l.shape))
+    is_pos = l != 0
+    is_neg = np.logical_not(is_pos)
+    is_correct = np.logical_xor(s < 0, is_pos)
+    return np.array([is_pos.sum(), is_neg.sum(), is_correct[is_pos].sum(), is_correct[is_neg].sum()], dtype=np.int64)
+
+
+def _accuracy(n_pos: int, n_neg: int, c_pos: int, c_neg: int) -> Tuple[float, float, float]:
+    n_all = n_pos + n_neg
+    return ((c_pos + c_neg) / n_all if n_all else float("nan"), c_pos / (n_pos + 1), c_neg / n_neg if n_neg else float("nan"))
+
+
+def compute_accuracy(scores, labels) -> Tuple[float, float, float]:
+    """(accuracy_all, accuracy_pos, accuracy_neg) of processing_tools.compute_accuracy (util/processing_tools.py:24-35): a pixel is
+    positive where labels != 0 and right where (scores < 0) XOR positive.  accuracy_pos keeps the reference's / (num_pos + 1);
+    accuracy_neg is nan when there is no negative pixel (the reference's 0 / 0)."""
+    return _accuracy(*(int(v) for v in accuracy_counts(scores, labels)))
+
+
+def accuracy_from_counts(counts) -> Tuple[float, float, float]:
+    """compute_accuracy's three fractions from integer counts [B, 4] (or [4]) of (n_pos, n_neg, correct_pos, correct_neg), summed over
+    the batch: compute_accuracy over the whole batch's pixels, the same integer sums and one float64 division each."""
+    c = np.asarray(counts.cpu() if hasattr(counts, "cpu") else counts)
+    if c.ndim not in (1, 2) or c.shape[-1] != 4 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("counts: expected integers [B, 4] or [4], got %s %s" % (c.dtype, c.shape))
+    return _accuracy(*(int(v) for v in c.reshape(-1, 4).sum(axis=0)))
+
+
+class TrainLog:
+    """The train loops' running numbers and log lines (CMPC_video/trainval_video.py:102-121; test.py:107-127 prints the same):
+
+        log = TrainLog(iters_per_log=100)
+        for n_iter in range(max_iter):
+            step, scal = feeder.step(accuracy=True)
+            log.add(n_iter, scal["loss_last"], scal["learning_rate"], scal["accuracy_counts"])
+            for line in log.lines(n_iter): print(line)
+
+    add() only stores what it is given: device tensors are not read, so nothing synchronises per step.  lines(n_iter) returns the three
+    lines when n_iter % iters_per_log == 0 (else none); the stored values are read then, or on flush(), and the 0.99-decay averages
+    (cls_loss_avg, avg_accuracy_all / pos / neg, all starting at 0) are replayed on the host in float64 in step order -- the per-step
+    loop's result.  `loss` stands for model.cls_loss (the `loss_last` scalar), `counts` for compute_accuracy's integer sums [B, 4]."""
+
+    def __init__(self, iters_per_log: int = 100, decay: float = 0.99):
+        if iters_per_log < 1:
+            raise ValueError("iters_per_log must be >= 1, got %r" % (iters_per_log,))
+        self.iters_per_log, self.decay = int(iters_per_log), float(decay)
+        self.cls_loss_avg = 0.0
+        self.avg_accuracy_all = self.avg_accuracy_pos = self.avg_accuracy_neg = 0.0
+        self.last = None                             # (n_iter, loss, lr, accuracy_all, accuracy_pos, accuracy_neg) of the last step replayed
+        self._pending: List[tuple] = []
+
+    def add(self, n_iter: int, loss, lr, counts):
+        self._pending.append((n_iter, loss, lr, counts))
+
+    def flush(self):
+        """Read every stored step (this is where device values cross to the host) and fold it into the averages, in step order."""
+        d = self.decay
+        for n_iter, loss, lr, counts in self._pending:
+            loss, lr = float(loss), float(lr)
+            a, p, n = accuracy_from_counts(counts)
+            self.cls_loss_avg = d * self.cls_loss_avg + (1 - d) * loss
+            self.avg_accuracy_all = d * self.avg_accuracy_all + (1 - d) * a
+            self.avg_accuracy_pos = d * self.avg_accuracy_pos + (1 - d) * p
+            self.avg_accuracy_neg = d * self.avg_accuracy_neg + (1 - d) * n
+            self.last = (n_iter, loss, lr, a, p, n)
+        self._pending = []
+
+    def lines(self, n_iter: int) -> List[str]:
+        if n_iter % self.iters_per_log != 0:
+            return []
+        self.flush()
+        if self.last is None or self.last[0] != n_iter:
+            raise ValueError("TrainLog.lines(%d): that step was not added" % n_iter)
+        _, loss, lr, a, p, n = self.last
+        return ['iter = %d, loss (cur) = %f, loss (avg) = %f, lr = %f' % (n_iter, loss, self.cls_loss_avg, lr),
+                'iter = %d, accuracy (cur) = %f (all), %f (pos), %f (neg)' % (n_iter, a, p, n),
+                'iter = %d, accuracy (avg) = %f (all), %f (pos), %f (neg)' % (n_iter, self.avg_accuracy_all, self.avg_accuracy_pos, self.avg_accuracy_neg)]

@@ -427,38 +427,70 @@ class LSTM_model(object):
             feats, ev = self.features_async(frames.contiguous())
             return self._video_fetch(feats, ev, torch.from_numpy(we), torch.from_numpy(sl))
 
-    def train_step_video(self, words, im, target_fine, valid_idx, clip):
-        """sess.run([train_step, cls_loss, learning_rate, pred, target], feed) (trainval_video.py:93-101)."""
+    def train_step_video(self, words, im, target_fine, valid_idx, clip, accuracy: bool = False):
+        """sess.run([train_step, cls_loss, learning_rate, pred, target], feed) (trainval_video.py:93-101).  accuracy=True adds
+        scal["accuracy_counts"] (train_step's docstring): compute_accuracy(model.pred, model.target)'s integer sums, on the device."""
         if self.mode != 'train':
             raise RuntimeError("model was built with mode='eval'")
         with torch.cuda.device(self.device):
             if len(self._inflight) >= self.MAX_STEPS_IN_FLIGHT:
                 self._inflight.pop(0).synchronize()
             we, sl, fr = self._video_feeds(words, valid_idx, clip)
-            if self.bb_trainer is not None:
-                return self._train_step_conv5(we, fr, target_fine, sl)
-            feats, ev = self.features_async(fr)
-            self.loss_and_grads(feats, we, target_fine, sl, after=ev)
-            sv = self.eng.tap("scalars").clone()
-            ost = self.opt_stream if self.opt_stream is not None else torch.cuda.current_stream(self.device)
-            for b in range(self.eng.n_buckets):
-                with torch.cuda.stream(ost):
-                    lr = self.eng.optimizer_bucket(b, 1.0)
-            done = torch.cuda.Event()
-            done.record(ost)
-            self._inflight.append(done)
+            return self._train_step_video(we, sl, fr, target_fine, None, accuracy)
+
+    def train_step_video_frames(self, words_end, seq_len, frames, target_fine, ready=None, accuracy: bool = False):
+        """train_step_video on a device feed, the training twin of forward_video_frames: `frames` = the clip's sampled frames (FRAME_IDX)
+        as BGR - mu, a float32 [5, H, W, 3] tensor on the model's device; target_fine a float32 [1, H, W, 1] tensor there; words_end
+        [1, T] / seq_len [1] in video_words' output form (END-padded ids and the length), host or device int32.  ready: an event
+        recorded once `frames` was complete; the backbone stream then waits for it alone instead of the caller's stream (features_async),
+        as in train_step.  Words, length and target are read on the caller's stream, which must be ordered behind them.  Returns
+        what train_step_video returns, bit-identical in scalars and in the state afterwards to train_step_video on a clip whose frames
+        FRAME_IDX are `frames`: only 5 of the 16 frames ever reach the graph (vid:70)."""
+        if self.mode != 'train':
+            raise RuntimeError("model was built with mode='eval'")
+        self._check_video_frames(frames)
+        B, T, H, W = 1, self.num_steps, self.H, self.W
+        if tuple(words_end.shape) != (B, T) or tuple(seq_len.shape) != (B,):
+            raise ValueError(f"words_end must be [{B},{T}] and seq_len [{B}], got {tuple(words_end.shape)}, {tuple(seq_len.shape)}")
+        if not torch.is_tensor(target_fine) or target_fine.device != self.device or target_fine.dtype != torch.float32 \
+                or tuple(target_fine.shape) != (B, H, W, 1):
+            raise ValueError(f"target_fine must be a float32 [{B},{H},{W},1] tensor on {self.device}")
+        with torch.cuda.device(self.device):
+            if len(self._inflight) >= self.MAX_STEPS_IN_FLIGHT:
+                self._inflight.pop(0).synchronize()
+            return self._train_step_video(words_end, seq_len, frames.contiguous(), target_fine, ready, accuracy)
+
+    def _train_step_video(self, we, sl, fr, target_fine, ready, accuracy):
+        """The video train step on END-padded ids, the length and the 5 sampled frames on the device (inside the device scope)."""
+        if self.bb_trainer is not None:
+            return self._train_step_conv5(we, fr, target_fine, sl, accuracy=accuracy)
+        feats, ev = self.features_async(fr, ready)
+        o = self.loss_and_grads(feats, we, target_fine, sl, after=ev, accuracy=accuracy)
+        sv = self.eng.tap("scalars").clone()
+        ost = self.opt_stream if self.opt_stream is not None else torch.cuda.current_stream(self.device)
+        for b in range(self.eng.n_buckets):
+            with torch.cuda.stream(ost):
+                lr = self.eng.optimizer_bucket(b, 1.0)
+        done = torch.cuda.Event()
+        done.record(ost)
+        self._inflight.append(done)
         scal = {k: sv[i] for i, k in enumerate(self._SCALARS)}
         scal["mean_IOU"] = scal.pop("mIoU")
         scal["learning_rate"] = lr
+        if accuracy:
+            scal["accuracy_counts"] = o["accuracy_counts"]
         return self.eng.step, scal
 
     def predict(self, images, sentences, sequence_lenghts):
         """TF-serving signature of export_model_serving.py:57-71: images, sentences, sequence_lenghts -> masks."""
         return self.forward(sentences, images, sequence_lenghts)["sigm"]
 
-    def loss_and_grads(self, feats, words, target_fine, seq_len, after=None, im=None, between=None):
+    def loss_and_grads(self, feats, words, target_fine, seq_len, after=None, im=None, between=None, accuracy: bool = False):
         """forward + backward of `cost` (CMPC_model.py:447) into the flat gradient buffer: cmpc_forward + cmpc_backward
-        (L2 and the x2 bias multiplier are applied inside the Adam kernel)."""
+        (L2 and the x2 bias multiplier are applied inside the Adam kernel).  accuracy: one cmpc_train_accuracy launch on the caller's
+        stream between the two, on the handle's `pred` tap and the step's device target (the backward pass leaves `pred` alone, but
+        right behind the forward pass it is the forward pass's value whatever the backward pass does); the fetch dict then holds
+        `accuracy_counts`, a fresh int64 [B, 4] tensor."""
         ld = None
         if between is not None:                  # work the caller wants enqueued behind the levels' forward (the next batch's backbone)
             if self._levels_done is None:
@@ -467,21 +499,32 @@ class LSTM_model(object):
             ld = self._levels_done
         o = self.head(feats, words, seq_len, target_fine, after=after, im=im, levels_done=ld)
         with torch.cuda.device(self.device):
+            if accuracy:
+                from .evaluate import train_accuracy
+                o["accuracy_counts"] = train_accuracy(o["pred"], self._keep[-1][2])
             if between is not None:
                 between(ld)
             self.eng.backward()
         return o
 
     _SCALARS = ("loss_all", "loss_c3", "loss_c4", "loss_c5", "loss_last", "mIoU")
+    FRAME_IDX = FRAME_IDX                  # the clip positions the video graph samples (vid:70)
     MAX_STEPS_IN_FLIGHT = int(os.environ.get("CMPC_STEPS_IN_FLIGHT", "2"))
 
-    def train_step(self, words, im, target_fine, seq_len, ready=None, next_im=None, next_ready=None, next_gate="fwd"):
+    def train_step(self, words, im, target_fine, seq_len, ready=None, next_im=None, next_ready=None, next_gate="fwd", accuracy: bool = False):
         """sess.run([train, train_step, merged], feed) (trainval_model.py:98-107).
         ready: optional torch.cuda.Event recorded once the (device-resident, prefetched) feeds were complete.
         next_im: the NEXT step's image batch, already resident on the device (a prefetching loader has it: util/data_reader_refvos.py:38-46),
         next_ready its event.  The frozen backbone of that batch is then enqueued behind THIS step's levels' forward, where the step is a
         serial chain of small launches (exchange modules, ConvLSTM, scores) until the levels' backward; the next call must pass the same
-        tensor as `im` and finds its taps ready.  Same arithmetic, same results: only the order on the device changes."""
+        tensor as `im` and finds its taps ready.  Same arithmetic, same results: only the order on the device changes.
+        accuracy=True: the train loops' compute_accuracy(model.pred, model.target) (test.py:94-127, util/processing_tools.py:24-35) without
+        leaving the device -- one cmpc_train_accuracy launch on the caller's stream; scal["accuracy_counts"] is an int64 [B, 4] device
+        tensor of (n_pos, n_neg, correct_pos, correct_neg) per sample, not synchronised like the other scalars
+        (hostutil.accuracy_from_counts / TrainLog read it).  The target is target_fine resized to the `pred` tap's own size: vf_h x vf_w
+        for CMPC_model and the video model, the reference's model.target.  For the CMPCv5 graphs the reference's pred and target sizes
+        differ and its driver has the accuracy commented out (trainval_model.py:111); resizing the target to pred's size (H/4 x W/4) there
+        is this project's definition.  With accuracy=False nothing changes: the same launches and the same keys."""
         if self.mode != 'train':
             raise RuntimeError("model was built with mode='eval' (CMPC_model.py:85-86)")
         self._check_feeds(words, im, seq_len, target_fine)
@@ -497,7 +540,7 @@ class LSTM_model(object):
                 imd = imd + float(self._aug_rng.uniform(-0.2, 0.2))
                 im = imd
             if self.bb_trainer is not None:
-                return self._train_step_conv5(words, imd, target_fine, seq_len)
+                return self._train_step_conv5(words, imd, target_fine, seq_len, accuracy=accuracy)
             pf, self._prefetched = self._prefetched, None
             if pf is not None and pf[0] is im:
                 feats, ev = pf[1], pf[2]
@@ -514,7 +557,7 @@ class LSTM_model(object):
                 self._bwd_levels = torch.cuda.Event()
                 self._bwd_levels.record()
                 _lib.call("cmpc_set_bwd_levels_event", self.eng.h, ctypes.c_void_p(self._bwd_levels.cuda_event))
-            self.loss_and_grads(feats, words, target_fine, seq_len, after=ev, im=imd, between=between)
+            o = self.loss_and_grads(feats, words, target_fine, seq_len, after=ev, im=imd, between=between, accuracy=accuracy)
             if pre and next_gate == "bwd":          # behind the levels' backward: beside the grouped dW launch and the text encoder's backward
                 self.bb_stream.wait_event(self._bwd_levels)
                 f2, e2 = self.features_async(next_im, next_ready if next_ready is not None else self._bwd_levels)
@@ -540,10 +583,12 @@ class LSTM_model(object):
         scal = {k: sv[i] for i, k in enumerate(self._SCALARS)}
         scal["mean_IOU"] = scal.pop("mIoU")
         scal["learning_rate"] = lr
+        if accuracy:
+            scal["accuracy_counts"] = o["accuracy_counts"]
         self.last = scal
         return self.eng.step, scal
 
-    def _train_step_conv5(self, words, imd, target_fine, seq_len):
+    def _train_step_conv5(self, words, imd, target_fine, seq_len, accuracy: bool = False):
         """conv5=True (CMPC_model.py:427-430, v5:521-525; finetune=True of the video model, vid:554-557): backbone forward with its
         activations kept, head forward / backward (which also returns d cost / d taps), backbone backward, one TF-Adam step over the head and
         the res3-res5 convolution weights.  Everything on the caller's stream (no side streams: the optional mode is not the benchmarked
@@ -551,7 +596,7 @@ class LSTM_model(object):
         h, w = self.cfg.vf_h, self.cfg.vf_w
         nb = imd.shape[0]
         feats = self.bb_trainer.forward(imd)
-        self.loss_and_grads(feats, words, target_fine, seq_len, im=imd if (self.v5 and self.cfg.hsv) else None)
+        o = self.loss_and_grads(feats, words, target_fine, seq_len, im=imd if (self.v5 and self.cfg.hsv) else None, accuracy=accuracy)
         sv = self.eng.tap("scalars").clone()
         dt = {5: self.eng.tap("dc5").view(nb, h, w, -1), 4: self.eng.tap("dc4").view(nb, h, w, -1)}
         if not self.v5:
@@ -575,6 +620,8 @@ class LSTM_model(object):
         scal = {k: sv[i] for i, k in enumerate(self._SCALARS)}
         scal["mean_IOU"] = scal.pop("mIoU")
         scal["learning_rate"] = lr
+        if accuracy:
+            scal["accuracy_counts"] = o["accuracy_counts"]
         self.last = scal
         return self.eng.step, scal
 

@@ -616,6 +616,28 @@ int cmpc_train_prep(const unsigned char* img, int64_t img_bytes, const cmpc_eval
                     int64_t ann_bytes, const cmpc_train_desc* ann_descs_host, int B, int H, int W, int order, unsigned char* proc_im,
                     float* feed, float* target_fine, uint64_t* pos, void* stream);
 
+/* One clip of the video model (CMPC_video_mm_tgraph_allvec) from raw frames: n_img images (1..CMPC_TAPS_MAX_FRAMES, the clip's sampled
+ * frames) through cmpc_eval_prep's kernel and ONE annotation (the key frame's) through cmpc_train_prep's, enqueued by one call.
+ * feed [n_img, H, W, 3] float32 is bit-identical to cmpc_eval_prep's, target_fine [1, H, W, 1] and pos [1] to cmpc_train_prep's; the
+ * descriptors get the same validation as in those entries, before anything is launched. */
+int cmpc_clip_prep(const unsigned char* img, int64_t img_bytes, const cmpc_eval_desc* img_descs_host, int n_img,
+                   const unsigned char* ann, int64_t ann_bytes, const cmpc_train_desc* ann_desc_host, int H, int W, int order,
+                   float* feed, float* target_fine, uint64_t* pos, void* stream);
+
+/* ---- Training accuracy (the train loops' compute_accuracy lines: test.py:94-127, CMPC_video/trainval_video.py:93-123).
+ *      counts [B][4] uint64 = {n_pos, n_neg, correct_pos, correct_neg} per sample: the exact integers of
+ *      compute_accuracy(pred[b], target[b]) (util/processing_tools.py:24-35) with target = tf.image.resize_bilinear(target_fine, [h, w])
+ *      (model.target; legacy resize, align_corners=False, float32 arithmetic as oracle/cmpc_torch.py:resize_bilinear, no FMA; the source
+ *      index is floor of the float32 product dst * (in / out), as in TensorFlow's kernel, where the oracle floors the float64 product:
+ *      the two differ only where that product is an integer in exact arithmetic and rounds to just below it in float32, e.g. 26 -> 22
+ *      at dst 11, and never for an integer or dyadic scale such as 320 -> 40),
+ *      is_pos = target != 0, is_correct = (pred < 0) XOR is_pos (a score of 0.0, -0.0 or NaN counts as predicted positive).
+ *      pred [B, h, w] and target_fine [B, H, W] float32 device pointers, h <= H, w <= W (h == H, w == W: the identity resize);
+ *      B <= CMPC_EVAL_MAX_BATCH.  One launch, one workgroup per sample; no memset, no atomics, no workspace: reruns are bit-identical
+ *      and a sample's counts do not depend on the batch around it.  accuracy_all = (correct_pos + correct_neg) / (n_pos + n_neg),
+ *      accuracy_pos = correct_pos / (n_pos + 1), accuracy_neg = correct_neg / n_neg (hostutil.accuracy_from_counts) --------------- */
+int cmpc_train_accuracy(const float* pred, const float* target_fine, int B, int h, int w, int H, int W, uint64_t* counts, void* stream);
+
 /* Host utility (no GPU): CRC-32C of `n` bytes, continuing from `crc` (0 to start) -- the checksum of TensorFlow's tensor-bundle
  * checkpoints (trainval_model.py:46-63 restores / saves them; cmpc-refseg_amd/tf_bundle.py reads and writes the format). */
 uint32_t cmpc_crc32c(uint32_t crc, const void* data, size_t n);
