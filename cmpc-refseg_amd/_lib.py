@@ -137,6 +137,14 @@ class TrainDesc(C.Structure):
 ANN_COLOR, ANN_PLAIN = 0, 1
 
 
+class JfDesc(C.Structure):
+    """cmpc_jf_desc"""
+    _fields_ = [("pred_off", C.c_int64), ("gt_off", C.c_int64), ("h", C.c_int), ("w", C.c_int), ("r", C.c_int), ("pad_", C.c_int)]
+
+
+JF_MAX_RADIUS = 128      # CMPC_JF_MAX_RADIUS
+
+
 class Fetches(C.Structure):
     """cmpc_fetches"""
     _fields_ = [("pred", C.c_void_p), ("up", C.c_void_p), ("sigm", C.c_void_p)]
@@ -254,6 +262,8 @@ SIGNATURES = {
     "cmpc_train_prep": [_P, _L, C.POINTER(EvalDesc), _P, _L, C.POINTER(TrainDesc), _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "cmpc_clip_prep": [_P, _L, C.POINTER(EvalDesc), _I, _P, _L, C.POINTER(TrainDesc), _I, _I, _I, _P, _P, _P, _P],
     "cmpc_train_accuracy": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "cmpc_mask_jf_workspace": [C.POINTER(JfDesc), _I, C.POINTER(_L)],
+    "cmpc_mask_jf": [_P, _L, _P, _L, C.POINTER(JfDesc), _I, _P, _P, _L, _P],
     "cmpc_taps_copy": [_I, _PP, _PP, C.POINTER(_L), _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _P],
     "cmpc_launch_trace": [_I, _P],
     "cmpc_launch_trace_read": [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_L)],

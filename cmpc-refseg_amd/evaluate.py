@@ -248,6 +248,130 @@ def train_accuracy(pred, target_fine, out: torch.Tensor = None) -> torch.Tensor:
     return counts
 
 
+# ---- J and F of video object segmentation: cmpc_mask_jf (include/cmpc.h; hostutil.jf_from_counts / JFEval turn the counts into scores) --
+JF_COUNTS = 6                  # I, U, n_pred, n_gt, pred_match, gt_match
+
+
+class JfPlan:
+    """One cmpc_mask_jf call: `n` samples and their descriptors.  Prediction offsets are as given.  With `gts` (host uint8 arrays) the
+    ground truths are packed at 16-byte aligned offsets for one upload (gt_offs, gt_bytes); with `gt_offs` they are where the caller
+    says.  ws_bytes: the workspace the call needs; idx: which of the caller's results each sample scores; counts_off: where the
+    caller keeps the counts."""
+    __slots__ = ("n", "descs", "gts", "gt_offs", "gt_bytes", "ws_bytes", "idx", "counts_off")
+
+    def __init__(self, sizes: Sequence[Tuple[int, int]], pred_offs: Sequence[int], gts: Optional[Sequence[np.ndarray]] = None,
+                 gt_offs: Optional[Sequence[int]] = None, bound_th: float = 0.008, idx: Optional[Sequence[int]] = None, counts_off: int = 0):
+        _check_batch(len(sizes))
+        self.n = len(sizes)
+        self.descs = (_lib.JfDesc * self.n)()
+        self.gts, self.gt_offs, off = (None if gts is None else list(gts)), [], 0
+        for i, ((h, w), po) in enumerate(zip(sizes, pred_offs)):
+            h, w = int(h), int(w)
+            r = HU.jf_radius(h, w, bound_th)
+            if r > _lib.JF_MAX_RADIUS:
+                raise ValueError("sample %d: radius %d at %d x %d exceeds %d" % (i, r, h, w, _lib.JF_MAX_RADIUS))
+            go = off if gt_offs is None else int(gt_offs[i])
+            self.descs[i] = _lib.JfDesc(int(po), go, h, w, r, 0)
+            self.gt_offs.append(_Offset(go))
+            off = max(off, go + -(-h * w // _ALIGN) * _ALIGN) if gt_offs is not None else off + -(-h * w // _ALIGN) * _ALIGN
+        self.gt_bytes = off
+        self.ws_bytes = jf_workspace(self.descs, self.n)
+        self.idx = list(range(self.n)) if idx is None else list(idx)
+        self.counts_off = int(counts_off)
+
+
+def jf_workspace(descs, n: int) -> int:
+    """cmpc_mask_jf_workspace: 2 * h * ceil(w / 64) 64-bit words per sample, in bytes."""
+    import ctypes
+    out = ctypes.c_int64()
+    _lib.call("cmpc_mask_jf_workspace", descs, n, ctypes.byref(out))
+    return out.value
+
+
+class _JfDevice:
+    """The device half of scoring, shared by mask_jf and the two segmenters: the plan's ground truths go up through a pinned _Staging
+    of their own (or are read where they lie, gt_ptr), cmpc_mask_jf reads the predictions where they lie and writes the counts where
+    it is told, all on the current stream.  The workspace grows only when a call needs more than any before it."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.staging = _Staging(self.device)
+        self.ws = None
+
+    def score(self, pred_ptr: int, pred_bytes: int, plan: JfPlan, counts_ptr: int, gt_ptr: Optional[int] = None, gt_bytes: int = 0):
+        with torch.cuda.device(self.device):
+            if self.ws is None or self.ws.numel() * 8 < plan.ws_bytes:
+                self.ws = torch.empty(max(plan.ws_bytes // 8, 1 << 15), dtype=torch.int64, device=self.device)
+            if gt_ptr is None:
+                gt_ptr, gt_bytes = self.staging.upload(plan.gts, plan.gt_offs, plan.gt_bytes).data_ptr(), plan.gt_bytes
+            _lib.call("cmpc_mask_jf", pred_ptr, pred_bytes, gt_ptr, gt_bytes, plan.descs, plan.n, counts_ptr,
+                      self.ws.data_ptr(), self.ws.numel() * 8, torch.cuda.current_stream(self.device).cuda_stream)
+
+
+_JF_DEVICE: Dict[str, _JfDevice] = {}
+
+
+def _mask_addresses(masks, first: int, dev, kind: str):
+    """(sizes, device addresses) of a chunk of [h, w] masks: contiguous uint8 tensors on `dev` where they lie, host arrays packed
+    into one upload through the `kind` staging."""
+    sizes, addr, host = [], [], []
+    for i, m in enumerate(masks):
+        if torch.is_tensor(m):
+            if m.device != dev or m.dtype != torch.uint8 or m.dim() != 2 or not m.is_contiguous() or m.numel() == 0:
+                raise ValueError("mask %d: a tensor must be a contiguous uint8 [h, w] on %s, got %s %s on %s"
+                                 % (first + i, dev, m.dtype, tuple(m.shape), m.device))
+            sizes.append((int(m.shape[0]), int(m.shape[1])))
+            addr.append(m.data_ptr())
+        else:
+            try:
+                a = _masks_u8([m])[0]
+            except ValueError as e:
+                raise ValueError("mask %d: %s" % (first + i, str(e).split(": ", 1)[-1])) from None
+            sizes.append(a.shape)
+            addr.append(None)
+            host.append((i, a))
+    if host:
+        offs, off = [], 0
+        for _, a in host:
+            offs.append(_Offset(off))
+            off += -(-a.size // _ALIGN) * _ALIGN
+        up = _staging(dev, kind).upload([a for _, a in host], offs, off)
+        for (i, _), o in zip(host, offs):
+            addr[i] = up.data_ptr() + o.offset
+    return sizes, addr
+
+
+def mask_jf(preds, gts, bound_th: float = 0.008, device="cuda:0") -> np.ndarray:
+    """The six integers of cmpc_mask_jf (I, U, n_pred, n_gt, pred_match, gt_match) for every (prediction, ground truth) pair: two lists
+    of [h, w] masks, non-zero = foreground, each pair of one size and the pairs of any sizes.  Host arrays are packed and uploaded;
+    contiguous uint8 device tensors are read in place.  The dilation radius is hostutil.jf_radius(h, w, bound_th).  Runs in chunks of
+    MAX_BATCH on the current stream and synchronises once, at the end: returns int64 [n, 6] (hostutil.jf_from_counts, JFEval)."""
+    preds, gts = list(preds), list(gts)
+    if len(preds) != len(gts) or not preds:
+        raise ValueError("mask_jf: %d predictions and %d ground truths" % (len(preds), len(gts)))
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    key = str(dev)
+    if key not in _JF_DEVICE:
+        _JF_DEVICE[key] = _JfDevice(dev)
+    jd = _JF_DEVICE[key]
+    n = len(preds)
+    with torch.cuda.device(dev):
+        counts = torch.empty(n, JF_COUNTS, dtype=torch.int64, device=dev)
+        for s in range(0, n, MAX_BATCH):
+            sizes, pa = _mask_addresses(preds[s: s + MAX_BATCH], s, dev, "jf_pred")
+            gsizes, ga = _mask_addresses(gts[s: s + MAX_BATCH], s, dev, "jf_gt")
+            for i, (a, b) in enumerate(zip(sizes, gsizes)):
+                if a != b:
+                    raise ValueError("mask_jf: pair %d: prediction %s, ground truth %s" % (s + i, a, b))
+            pb, gb = min(pa), min(ga)
+            plan = JfPlan(sizes, [a - pb for a in pa], gt_offs=[a - gb for a in ga], bound_th=bound_th)
+            jd.score(pb, max(a + h * w for a, (h, w) in zip(pa, sizes)) - pb, plan, counts[s: s + len(sizes)].data_ptr(),
+                     gt_ptr=gb, gt_bytes=max(a + h * w for a, (h, w) in zip(ga, sizes)) - gb)
+        return counts.cpu().numpy()
+
+
 def unpack_masks(buf, descs) -> list:
     """The [h, w] views of a packed mask buffer (device tensor or NumPy array) at its descriptors' offsets."""
     if torch.is_tensor(buf):

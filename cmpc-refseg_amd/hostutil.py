@@ -338,3 +338,83 @@ class TrainLog:
         return ['iter = %d, loss (cur) = %f, loss (avg) = %f, lr = %f' % (n_iter, loss, self.cls_loss_avg, lr),
                 'iter = %d, accuracy (cur) = %f (all), %f (pos), %f (neg)' % (n_iter, a, p, n),
                 'iter = %d, accuracy (avg) = %f (all), %f (pos), %f (neg)' % (n_iter, self.avg_accuracy_all, self.avg_accuracy_pos, self.avg_accuracy_neg)]
+
+
+# ---- J and F of video object segmentation (the ranking of Refer-YouTube-VOS and Refer-DAVIS) -------------------------------------------
+# Restated from the DAVIS-2017 evaluation code (db_eval_iou, f_measure, db_statistics), which neither the reference nor this project
+# holds a copy of: parity against it is UNPINNED.  The integer counts come from cmpc_mask_jf (evaluate.mask_jf, the segmenters).
+JF_KEYS = ("J_mean", "J_recall", "J_decay", "F_mean", "F_recall", "F_decay")
+
+
+def jf_radius(h: int, w: int, bound_th: float = 0.008) -> int:
+    """f_measure's dilation radius in pixels: bound_th itself when it is >= 1 (a whole number of pixels), else
+    ceil(bound_th * sqrt(h^2 + w^2)) in float64 -- 12 at 720 x 1280."""
+    if h < 1 or w < 1 or not bound_th > 0:
+        raise ValueError("jf_radius: mask %r x %r, bound_th %r" % (h, w, bound_th))
+    if bound_th >= 1:
+        if bound_th != int(bound_th):
+            raise ValueError("jf_radius: bound_th %r >= 1 must be a whole number of pixels" % (bound_th,))
+        return int(bound_th)
+    return int(np.ceil(np.float64(bound_th) * np.sqrt(np.float64(h) * h + np.float64(w) * w)))
+
+
+def jf_from_counts(c) -> Tuple[float, float]:
+    """(J, F) in float64 from one sample's (I, U, n_pred, n_gt, pred_match, gt_match).  J = I / U, 1 when both masks are empty.
+    Precision = pred_match / n_pred and recall = gt_match / n_gt, with f_measure's rules for an empty boundary map: (1, 0) when only
+    the prediction's is empty, (0, 1) when only the ground truth's, (1, 1) when both; F = 2 P R / (P + R), 0 when P + R = 0."""
+    I, U, n_pred, n_gt, pm, gm = (int(v) for v in np.asarray(c).reshape(6))
+    J = 1.0 if U == 0 else I / U
+    if n_pred == 0 and n_gt > 0:
+        P, R = 1.0, 0.0
+    elif n_gt == 0 and n_pred > 0:
+        P, R = 0.0, 1.0
+    elif n_pred == 0 and n_gt == 0:
+        P, R = 1.0, 1.0
+    else:
+        P, R = pm / n_pred, gm / n_gt
+    return J, (0.0 if P + R == 0 else 2 * P * R / (P + R))
+
+
+def jf_decay_bins(n: int) -> List[Tuple[int, int]]:
+    """db_statistics' four bins of a sequence of n frames as (first, last) frame positions, both inclusive: the edges are
+    round(linspace(1, n, 5) + 1e-10) - 1 and bin i runs from edge i to edge i + 1."""
+    ids = (np.round(np.linspace(1, n, 5) + 1e-10) - 1).astype(np.int64)
+    return [(int(ids[i]), int(ids[i + 1])) for i in range(4)]
+
+
+def _jf_stats(v: np.ndarray) -> Tuple[float, float, float]:
+    """db_statistics: mean, recall (share of frames > 0.5) and decay (first bin's mean minus the last bin's) of per-frame values."""
+    bins = jf_decay_bins(len(v))
+    (a0, a1), (b0, b1) = bins[0], bins[3]
+    return float(np.mean(v)), float(np.mean(v > 0.5)), float(np.mean(v[a0: a1 + 1]) - np.mean(v[b0: b1 + 1]))
+
+
+class JFEval:
+    """Per-sequence J and F, as the benchmarks average them: a sequence is one (video, expression) pair.
+
+        jf = JFEval(); jf.add(seq, frame, counts) ...; jf.result()
+
+    counts: the six integers of cmpc_mask_jf for that frame.  result() -> {"J_mean", "J_recall", "J_decay", "F_mean", "F_recall",
+    "F_decay"} averaged over the sequences (each sequence's statistics over its frames in frame order, _jf_stats), "J&F" =
+    (J_mean + F_mean) / 2, "sequences", "frames", and "per_sequence": {seq: the six statistics and "frames"}."""
+
+    def __init__(self):
+        self.seqs: Dict[object, Dict[int, Tuple[float, float]]] = {}
+
+    def add(self, seq, frame: int, counts):
+        frames = self.seqs.setdefault(seq, {})
+        if frame in frames:
+            raise ValueError("JFEval.add: sequence %r already holds frame %r" % (seq, frame))
+        frames[frame] = jf_from_counts(counts)
+
+    def result(self) -> Dict[str, object]:
+        if not self.seqs:
+            raise ValueError("JFEval.result: no frames")
+        per = {}
+        for seq, frames in self.seqs.items():
+            jf = np.array([frames[f] for f in sorted(frames)], dtype=np.float64)
+            per[seq] = dict(zip(JF_KEYS, _jf_stats(jf[:, 0]) + _jf_stats(jf[:, 1])), frames=len(frames))
+        out: Dict[str, object] = {k: float(np.mean([p[k] for p in per.values()])) for k in JF_KEYS}
+        out["J&F"] = (out["J_mean"] + out["F_mean"]) / 2
+        out["sequences"], out["frames"], out["per_sequence"] = len(per), sum(p["frames"] for p in per.values()), per
+        return out

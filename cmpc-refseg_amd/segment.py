@@ -37,7 +37,7 @@ from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, hostutil as HU
-from .evaluate import MAX_BATCH, _check_dcrf_method, _images_u8, check_gv_norm, gv_norm_scope, plan_masks, plan_prep
+from .evaluate import JF_COUNTS, MAX_BATCH, JfPlan, _check_dcrf_method, _images_u8, check_gv_norm, gv_norm_scope, plan_masks, plan_prep
 
 
 def half_size(h: int, w: int) -> Tuple[int, int]:
@@ -79,6 +79,46 @@ def check_expression(i: int, ex, vocab, T: int) -> Tuple[np.ndarray, int]:
     return ids.astype(np.int32), n
 
 
+def check_ground_truth(e: int, f: int, gt, size: Tuple[int, int]) -> np.ndarray:
+    """What run(ground_truth=...) returned for expression e and frame f -- a mask [oh, ow] (non-zero = object) or an (annotation, key)
+    pair cut with hostutil.object_mask -- as uint8 {0, 1} at the size of the yielded mask.  Raises ValueError naming (e, f)."""
+    try:
+        obj = HU.object_mask(gt[0], gt[1]) if isinstance(gt, tuple) and len(gt) == 2 else HU.object_mask(gt)
+    except ValueError as err:
+        raise ValueError("ground truth of (expression %d, frame %d): %s" % (e, f, err)) from None
+    if obj.shape != tuple(size):
+        raise ValueError("ground truth of (expression %d, frame %d): %s, the mask is %s (out_size of the frame)" % (e, f, obj.shape, tuple(size)))
+    return np.ascontiguousarray(obj).view(np.uint8)
+
+
+def plan_scoring(descs, pairs: Sequence[Tuple[int, np.ndarray]], nbytes: int, bound_th: float) -> Optional[JfPlan]:
+    """The cmpc_mask_jf call that scores results `i` of `descs` (the packed masks of one ring slot) against the ground truths of
+    `pairs` [(i, uint8 mask)]; None when the slot holds no annotated frame.  The counts ride at the 8-aligned tail of the slot."""
+    if not pairs:
+        return None
+    ds = [descs[i] for i, _ in pairs]
+    return JfPlan([(d.h, d.w) for d in ds], [d.offset for d in ds], gts=[g for _, g in pairs], bound_th=bound_th,
+                  idx=[i for i, _ in pairs], counts_off=scored_bytes(nbytes, 0))
+
+
+def scored_bytes(nbytes: int, n: int) -> int:
+    """Bytes of a ring slot that holds `nbytes` of packed masks and the counts of n of them behind, 8-byte aligned."""
+    return -(-nbytes // 8) * 8 + 8 * JF_COUNTS * n
+
+
+def slot_counts(host: np.ndarray, plan: JfPlan) -> np.ndarray:
+    """The int64 [n, 6] counts at the tail of a pinned slot."""
+    return host[plan.counts_off: plan.counts_off + 8 * JF_COUNTS * plan.n].view(np.int64).reshape(plan.n, JF_COUNTS)
+
+
+def _enqueue_scoring(stage, plan: JfPlan, nbytes: int) -> int:
+    """The device half both stages share: cmpc_mask_jf on the `nbytes` of masks cmpc_eval_mask_out left in stage.mask_dev, the counts
+    into the same buffer behind them.  Returns the bytes the slot's one copy now carries."""
+    base = stage.mask_dev.data_ptr()
+    stage.scorer.score(base, nbytes, plan, base + plan.counts_off)
+    return scored_bytes(nbytes, plan.n)
+
+
 class _DeviceStage:
     """The device half of FrameSegmenter.  All buffers are allocated once (the pinned ring and the device mask buffer grow only when a
     batch needs more bytes than any before it): two feed / proc_im sets that alternate with the frame batches, one device mask buffer,
@@ -86,7 +126,7 @@ class _DeviceStage:
 
     def __init__(self, model, nslots: int, threshold: float, value: int, dcrf: bool, dcrf_method: str):
         import torch
-        from .evaluate import _Staging
+        from .evaluate import _JfDevice, _Staging
         self.torch = torch
         self.model, self.threshold, self.value, self.dcrf, self.dcrf_method = model, threshold, value, dcrf, dcrf_method
         self.dev = model.device
@@ -96,6 +136,7 @@ class _DeviceStage:
             self.feed = [torch.empty(B, H, W, 3, dtype=torch.float32, device=self.dev) for _ in range(2)]
             self.proc = [torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.dev) for _ in range(2)]
             self.events = [torch.cuda.Event() for _ in range(nslots)]
+        self.scorer = _JfDevice(self.dev)
         self.nslots = nslots
         self.host: List = [None] * nslots
         self.mask_dev = None
@@ -135,8 +176,9 @@ class _DeviceStage:
             feats, done = m.features_async(feed)
         return feats, done, feed, proc
 
-    def segment(self, token, e: int, descs, nbytes: int, slot: int):
-        """Head of expression e on the batch's taps, the masks of its first len(descs) frames into ring slot `slot`."""
+    def segment(self, token, e: int, descs, nbytes: int, slot: int, jf: Optional[JfPlan] = None):
+        """Head of expression e on the batch's taps, the masks of its first len(descs) frames into ring slot `slot`; with `jf`, their
+        J / F counts behind them."""
         torch, m = self.torch, self.model
         feats, done, feed, proc = token
         n = len(descs)
@@ -152,6 +194,8 @@ class _DeviceStage:
             dt = _lib.EVAL_F32 if score.dtype == torch.float32 else _lib.EVAL_U8
             _lib.call("cmpc_eval_mask_out", score.data_ptr(), dt, n, m.H, m.W, float(thr), descs, self.mask_dev.data_ptr(),
                       self.mask_dev.numel(), self.value, torch.cuda.current_stream(self.dev).cuda_stream)
+            if jf is not None:
+                nbytes = _enqueue_scoring(self, jf, nbytes)
             self.host[slot][:nbytes].copy_(self.mask_dev[:nbytes], non_blocking=True)
             self.events[slot].record(torch.cuda.current_stream(self.dev))
 
@@ -174,7 +218,13 @@ class FrameSegmenter:
     thresholding the float32 sigm itself (test.py:307); with dcrf, the same resampling of the DenseCRF argmax on sigm / proc_im
     (test.py:309-322, crf.dense_crf_batch).  gv_norm: "sample" (default: the loop this replaces is batch 1) or "batch"; set for the
     run, the model's own mode restored when the generator ends or is closed.  depth: (frame batch, expression) results in flight behind
-    the one being handed out (depth + 1 pinned slots).  copy=False yields views of the pinned slot, valid until the next iteration."""
+    the one being handed out (depth + 1 pinned slots).  copy=False yields views of the pinned slot, valid until the next iteration.
+
+    run(..., ground_truth=fn) also scores the masks on the device (J and F, cmpc_mask_jf): fn(e, f) returns None for a frame without
+    annotation, a mask at out_size(h, w), or an (annotation, key) pair for hostutil.object_mask; it is called once per pair, on the
+    caller's thread, when that result is enqueued.  The counts travel with the masks and are added to `jf` (a hostutil.JFEval, kept
+    as self.jf; a fresh one when none is passed) under sequence (seq, e) and frame f as the masks are handed out; the yielded
+    triples are the same with and without it."""
 
     def __init__(self, model, vocab=None, threshold: float = 0.5, out_size: Callable[[int, int], Tuple[int, int]] = half_size, value: int = 255,
                  dcrf: bool = False, dcrf_method: str = "lattice", gv_norm: str = "sample", depth: int = 2, copy: bool = True, _stage=None):
@@ -192,6 +242,7 @@ class FrameSegmenter:
         self.depth, self.copy = int(depth), bool(copy)
         self.B, self.T, self.H, self.W = model.batch_size, model.num_steps, model.H, model.W
         self.nslots = self.depth + 1
+        self.jf, self.bound_th = None, 0.008
         self.stage = _stage if _stage is not None else _DeviceStage(model, self.nslots, self.threshold, self.value, self.dcrf, self.dcrf_method)
 
     def _batches(self, frames: Iterable) -> Iterator[Tuple[int, List[np.ndarray]]]:
@@ -219,20 +270,26 @@ class FrameSegmenter:
         descs, nbytes = plan_masks(sizes, self.H, self.W)
         return descs, nbytes
 
-    def run(self, frames: Iterable, expressions: Sequence) -> Iterator[Tuple[int, int, np.ndarray]]:
+    def run(self, frames: Iterable, expressions: Sequence, ground_truth: Optional[Callable] = None, jf: Optional[HU.JFEval] = None,
+            seq=None) -> Iterator[Tuple[int, int, np.ndarray]]:
         exprs = [check_expression(i, ex, self.vocab, self.T) for i, ex in enumerate(expressions)]
         if not exprs:
             raise ValueError("FrameSegmenter.run: no expressions")
+        if ground_truth is not None:
+            self.jf = jf if jf is not None else HU.JFEval()
         st = self.stage
         free = deque(range(self.nslots))
-        pending = deque()                          # (slot, e, first frame, descs) in enqueue order = yield order
+        pending = deque()                          # (slot, e, first frame, descs, scoring plan) in enqueue order = yield order
 
         def hand_out(block: bool):
             """Yield the masks of the oldest result(s) whose event has completed (waiting for the oldest one if `block`)."""
             while pending and (block or st.done(pending[0][0])):
-                slot, e, first, descs = pending.popleft()
+                slot, e, first, descs, plan = pending.popleft()
                 st.wait(slot)
                 host = st.view(slot)
+                if plan is not None:
+                    for i, c in zip(plan.idx, slot_counts(host, plan)):
+                        self.jf.add((seq, e), first + i, c)
                 for i, d in enumerate(descs):
                     mk = host[d.offset: d.offset + d.h * d.w].reshape(d.h, d.w)
                     yield e, first + i, (mk.copy() if self.copy else mk)
@@ -249,7 +306,7 @@ class FrameSegmenter:
                     return None
                 first, ims = nxt
                 descs, nbytes = self._plan(first, ims)
-                st.reserve(nbytes)
+                st.reserve(nbytes if ground_truth is None else scored_bytes(nbytes, len(descs)))
                 return first, descs, nbytes, st.begin(ims + [ims[0]] * (self.B - len(ims)))
 
             cur = begin_next()
@@ -262,8 +319,15 @@ class FrameSegmenter:
                     if not free:
                         yield from hand_out(True)
                     slot = free.popleft()
-                    st.segment(token, e, descs, nbytes, slot)
-                    pending.append((slot, e, first, descs))
+                    if ground_truth is None:
+                        plan = None
+                        st.segment(token, e, descs, nbytes, slot)
+                    else:
+                        gts = [(i, ground_truth(e, first + i)) for i in range(len(descs))]
+                        plan = plan_scoring(descs, [(i, check_ground_truth(e, first + i, g, (descs[i].h, descs[i].w)))
+                                                    for i, g in gts if g is not None], nbytes, self.bound_th)
+                        st.segment(token, e, descs, nbytes, slot, jf=plan)
+                    pending.append((slot, e, first, descs, plan))
                     yield from hand_out(False)
                 cur = nxt
             while pending:
@@ -326,7 +390,7 @@ class _ClipStage:
     def __init__(self, model, ring: int, nslots: int, score: str, threshold: float, value: int, dcrf: bool, dcrf_method: str):
         import ctypes
         import torch
-        from .evaluate import _Staging
+        from .evaluate import _JfDevice, _Staging
         from .model import FRAME_IDX
         self.torch, self.C = torch, ctypes
         self.model, self.score, self.threshold, self.value, self.dcrf, self.dcrf_method = model, score, threshold, value, dcrf, dcrf_method
@@ -345,6 +409,7 @@ class _ClipStage:
             self.proc_ring = torch.empty(ring, H, W, 3, dtype=torch.uint8, device=self.dev) if dcrf else None
             self.batch_ev = [torch.cuda.Event() for _ in range(ring // B + 2)]
             self.events = [torch.cuda.Event() for _ in range(nslots)]
+        self.scorer = _JfDevice(self.dev)
         self.bytes = [t[0].numel() * t.element_size() for t in taps]
         for b in self.bytes:
             if b % 16:
@@ -434,10 +499,13 @@ class _ClipStage:
             _lib.call("cmpc_eval_mask_out", score.data_ptr(), dt, 1, m.H, m.W, float(thr), self.C.byref(descs[e]), self.mask_dev.data_ptr(),
                       self.mask_dev.numel(), self.value, torch.cuda.current_stream(self.dev).cuda_stream)
 
-    def finish(self, f: int, slot: int, nbytes: int):
-        """Frame f's masks (every expression) into pinned slot `slot`, its event behind the copy."""
+    def finish(self, f: int, slot: int, nbytes: int, jf: Optional[JfPlan] = None):
+        """Frame f's masks (every expression) into pinned slot `slot`, its event behind the copy; with `jf`, their J / F counts
+        behind them."""
         torch = self.torch
         with torch.cuda.device(self.dev):
+            if jf is not None:
+                nbytes = _enqueue_scoring(self, jf, nbytes)
             self.host[slot][:nbytes].copy_(self.mask_dev[:nbytes], non_blocking=True)
             self.events[slot].record(torch.cuda.current_stream(self.dev))
 
@@ -469,7 +537,11 @@ class ClipSegmenter:
     is enqueued `lookahead` batches ahead of the first head that needs it and only when every frame it evicts is older than
     f - frames // 2 for the oldest frame f whose heads are not all enqueued (min_ring).  depth: frames whose masks are in flight behind
     the one being handed out (depth + 1 pinned slots); copy=False yields views of the pinned slot, valid until the next iteration.
-    stats after a run: {"frames": N, "backbone_passes": ceil(N / 5), "gathers": N, "heads": N * E}."""
+    stats after a run: {"frames": N, "backbone_passes": ceil(N / 5), "gathers": N, "heads": N * E}.
+
+    run(..., ground_truth=fn, jf=None, seq=None) scores the masks on the device as FrameSegmenter.run does: fn(e, f) is called for
+    e = 0 .. E - 1 when frame f's heads are enqueued, one cmpc_mask_jf call per frame scores its annotated expressions, and the counts
+    reach `jf` (self.jf) under sequence (seq, e) and frame f."""
 
     def __init__(self, model, vocab=None, score: str = "up", threshold: float = 1e-9, out_size: Callable[[int, int], Tuple[int, int]] = full_size,
                  value: int = 255, dcrf: bool = False, dcrf_method: str = "lattice", ring: int = 32, depth: int = 2, copy: bool = True,
@@ -497,6 +569,7 @@ class ClipSegmenter:
         self.T, self.H, self.W = model.num_steps, model.H, model.W
         self.nslots = self.depth + 1
         self.stats = {"frames": 0, "backbone_passes": 0, "gathers": 0, "heads": 0}
+        self.jf, self.bound_th = None, 0.008
         self.stage = _stage if _stage is not None else _ClipStage(model, self.ring, self.nslots, self.score, self.threshold, self.value,
                                                                   self.dcrf, self.dcrf_method)
 
@@ -510,16 +583,19 @@ class ClipSegmenter:
             raise ValueError("frame %d: out_size(%d, %d) = (%d, %d) is empty" % (f, a.shape[0], a.shape[1], oh, ow))
         return a, (int(oh), int(ow))
 
-    def run(self, frames: Iterable, expressions: Sequence) -> Iterator[Tuple[int, int, np.ndarray]]:
+    def run(self, frames: Iterable, expressions: Sequence, ground_truth: Optional[Callable] = None, jf: Optional[HU.JFEval] = None,
+            seq=None) -> Iterator[Tuple[int, int, np.ndarray]]:
         exprs = [check_expression(i, ex, self.vocab, self.T) for i, ex in enumerate(expressions)]
         if not exprs:
             raise ValueError("ClipSegmenter.run: no expressions")
+        if ground_truth is not None:
+            self.jf = jf if jf is not None else HU.JFEval()
         if len(exprs) > MAX_BATCH:
             raise ValueError("ClipSegmenter.run: %d expressions, at most %d per run" % (len(exprs), MAX_BATCH))
         st, B, E = self.stage, self.B, len(exprs)
         stats = self.stats = {"frames": 0, "backbone_passes": 0, "gathers": 0, "heads": 0}
         free = deque(range(self.nslots))
-        pending = deque()                          # (slot, frame, descs) in enqueue order = yield order
+        pending = deque()                          # (slot, frame, descs, scoring plan) in enqueue order = yield order
         sizes = deque()                            # out sizes of the frames read whose heads are not enqueued yet
         it = iter(frames)
         st.set_expressions(exprs)
@@ -527,9 +603,12 @@ class ClipSegmenter:
 
         def hand_out(block: bool):
             while pending and (block or st.done(pending[0][0])):
-                slot, fr, descs = pending.popleft()
+                slot, fr, descs, plan = pending.popleft()
                 st.wait(slot)
                 host = st.view(slot)
+                if plan is not None:
+                    for e, c in zip(plan.idx, slot_counts(host, plan)):
+                        self.jf.add((seq, e), fr, c)
                 for e, d in enumerate(descs):
                     mk = host[d.offset: d.offset + d.h * d.w].reshape(d.h, d.w)
                     yield e, fr, (mk.copy() if self.copy else mk)
@@ -569,17 +648,25 @@ class ClipSegmenter:
             # frame f + ahead was read, or the video ended and `read` is its length
             idx = sampled_frames(f, read, self.frames)
             descs, nbytes = plan_masks([sizes.popleft()] * E, self.H, self.W)
-            st.reserve(nbytes)
+            st.reserve(nbytes if ground_truth is None else scored_bytes(nbytes, E))
             if not free:
                 yield from hand_out(True)
             slot = free.popleft()
+            plan = None
+            if ground_truth is not None:
+                gts = [(e, ground_truth(e, f)) for e in range(E)]
+                plan = plan_scoring(descs, [(e, check_ground_truth(e, f, g, (descs[e].h, descs[e].w))) for e, g in gts if g is not None],
+                                    nbytes, self.bound_th)
             st.gather(f, idx)
             stats["gathers"] += 1
             for e in range(E):
                 st.head(f, e, descs, slot)
                 stats["heads"] += 1
-            st.finish(f, slot, nbytes)
-            pending.append((slot, f, descs))
+            if ground_truth is None:
+                st.finish(f, slot, nbytes)
+            else:
+                st.finish(f, slot, nbytes, jf=plan)
+            pending.append((slot, f, descs, plan))
             f += 1
             stats["frames"] = f
             yield from hand_out(False)

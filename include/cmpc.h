@@ -638,6 +638,30 @@ int cmpc_clip_prep(const unsigned char* img, int64_t img_bytes, const cmpc_eval_
  *      accuracy_pos = correct_pos / (n_pos + 1), accuracy_neg = correct_neg / n_neg (hostutil.accuracy_from_counts) --------------- */
 int cmpc_train_accuracy(const float* pred, const float* target_fine, int B, int h, int w, int H, int W, uint64_t* counts, void* stream);
 
+/* ---- J and F of video object segmentation (the measures Refer-YouTube-VOS and Refer-DAVIS are ranked by) as exact integers, for B
+ *      (prediction, ground truth) pairs of any sizes per call.  The definitions restate the DAVIS-2017 evaluation code (db_eval_iou,
+ *      f_measure / seg2bmap), which this project has no copy of: parity against it is unpinned (csrc/ops_jf.hip states the rules,
+ *      tests/jf_ref.py repeats them in NumPy).  Descriptors are HOST memory, validated before anything is launched and passed by value.
+ *      counts[b] = {I, U, n_pred, n_gt, pred_match, gt_match}:
+ *        I, U                   |pred & gt|, |pred | gt|
+ *        n_pred, n_gt           pixels of the boundary maps bmap(pred), bmap(gt)
+ *        pred_match, gt_match   pixels of bmap(pred) with a pixel of bmap(gt) at an offset dx^2 + dy^2 <= r^2 inside the image, and
+ *                               the same with the roles swapped (a binary dilation by a disc of radius r)
+ *      hostutil.jf_radius gives the measure's r = ceil(0.008 * diagonal), hostutil.jf_from_counts J and F.  The call clears the B x 6
+ *      words on the stream and then writes them (it does not accumulate); the integers do not depend on the order of the work.  ws:
+ *      device scratch of cmpc_mask_jf_workspace's size, 2 * h * ceil(w / 64) 64-bit words per sample (the two boundary maps as bits),
+ *      8-byte aligned; nothing but counts and ws is written.  B in 1..CMPC_EVAL_MAX_BATCH --------------------------------------------- */
+#define CMPC_JF_MAX_RADIUS 128
+typedef struct {
+    int64_t pred_off, gt_off;        /* byte offsets of the [h, w] uint8 masks in `pred` / `gt`; non-zero = foreground */
+    int h, w;
+    int r;                           /* dilation radius in pixels, 1..CMPC_JF_MAX_RADIUS */
+    int pad_;
+} cmpc_jf_desc;
+int cmpc_mask_jf_workspace(const cmpc_jf_desc* descs_host, int B, int64_t* bytes);
+int cmpc_mask_jf(const unsigned char* pred, int64_t pred_bytes, const unsigned char* gt, int64_t gt_bytes,
+                 const cmpc_jf_desc* descs_host, int B, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
+
 /* Host utility (no GPU): CRC-32C of `n` bytes, continuing from `crc` (0 to start) -- the checksum of TensorFlow's tensor-bundle
  * checkpoints (trainval_model.py:46-63 restores / saves them; cmpc-refseg_amd/tf_bundle.py reads and writes the format). */
 uint32_t cmpc_crc32c(uint32_t crc, const void* data, size_t n);
