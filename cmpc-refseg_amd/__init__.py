@@ -15,7 +15,7 @@ def __getattr__(name):
     if name in ("LSTM_model", "get_segmentation_model"):
         from . import model
         return getattr(model, name)
-    if name in ("model", "backbone", "dist", "engine", "checkpoint", "hostutil", "evaluate", "feed"):
+    if name in ("model", "backbone", "dist", "engine", "checkpoint", "hostutil", "evaluate", "feed", "visualize"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

@@ -143,6 +143,8 @@ class JfDesc(C.Structure):
 
 
 JF_MAX_RADIUS = 128      # CMPC_JF_MAX_RADIUS
+VIS_PRED, VIS_GT = 0, 1                   # CMPC_VIS_* kinds of cmpc_vis_overlay
+VIS_SIGMOID, VIS_AUTO = 1, 2              # CMPC_VIS_* flags of cmpc_vis_heat
 
 
 class Fetches(C.Structure):
@@ -264,6 +266,10 @@ SIGNATURES = {
     "cmpc_train_accuracy": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "cmpc_mask_jf_workspace": [C.POINTER(JfDesc), _I, C.POINTER(_L)],
     "cmpc_mask_jf": [_P, _L, _P, _L, C.POINTER(JfDesc), _I, _P, _P, _L, _P],
+    "cmpc_vis_overlay": [_I, _P, _L, C.POINTER(EvalDesc), _P, _L, C.POINTER(EvalDesc), _I, _P, _L, C.POINTER(EvalDesc), _P],
+    "cmpc_vis_heat_workspace": [_I, _I, C.POINTER(_L)],
+    "cmpc_vis_heat": [_P, _I, _I, _I, C.POINTER(EvalDesc), _I, C.c_double, C.c_double, _P, _P, _L, _P, _L, C.POINTER(EvalDesc), _P, _P, _L, _P],
+    "cmpc_vis_words": [_P, _I, _I, _I, _I, C.POINTER(_I), _I, _I, _I, _I, _P, _P, _L, _P],
     "cmpc_taps_copy": [_I, _PP, _PP, C.POINTER(_L), _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _P],
     "cmpc_launch_trace": [_I, _P],
     "cmpc_launch_trace_read": [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_L)],

@@ -132,9 +132,9 @@ def _staging(device, kind: str) -> _Staging:
     return _STAGING[key]
 
 
-def prepare_images(images, H: int, W: int, device="cuda:0") -> Tuple[torch.Tensor, torch.Tensor]:
-    """resize_and_pad + img_as_ubyte + BGR - mu of original-size uint8 images ([h, w, 3] or [h, w]) on the device:
-    (feed float32 [B, H, W, 3], proc_im uint8 [B, H, W, 3]).  Enqueued on the current stream; nothing synchronises."""
+def _prepare_images(images, H: int, W: int, device):
+    """prepare_images' work: (feed, proc_im, the packed source images on the device, their descriptors, the packed length).  The source
+    buffer is a staging slot: it holds these bytes until the second call after this one enqueues its upload on the same stream."""
     ims = _images_u8(images)
     descs, nbytes = plan_prep([a.shape for a in ims], H, W)
     dev = torch.device(device)
@@ -145,6 +145,13 @@ def prepare_images(images, H: int, W: int, device="cuda:0") -> Tuple[torch.Tenso
         feed = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
         _lib.call("cmpc_eval_prep", src.data_ptr(), nbytes, descs, B, H, W, proc.data_ptr(), feed.data_ptr(),
                   torch.cuda.current_stream(dev).cuda_stream)
+    return feed, proc, src, descs, nbytes
+
+
+def prepare_images(images, H: int, W: int, device="cuda:0") -> Tuple[torch.Tensor, torch.Tensor]:
+    """resize_and_pad + img_as_ubyte + BGR - mu of original-size uint8 images ([h, w, 3] or [h, w]) on the device:
+    (feed float32 [B, H, W, 3], proc_im uint8 [B, H, W, 3]).  Enqueued on the current stream; nothing synchronises."""
+    feed, proc, _, _, _ = _prepare_images(images, H, W, device)
     return feed, proc
 
 
@@ -154,11 +161,8 @@ def _upload_masks(masks, H, W, device):
     return ms, descs, nbytes, _staging(device, "gt").upload(ms, descs, nbytes)
 
 
-def mask_iu(score_map, gt_masks, thresh: float = 1e-9, want_masks: bool = False, out: torch.Tensor = None):
-    """(I, U) per sample of compute_mask_IU(resize_and_crop(score_map >= thresh, mh, mw), gt) on the device.
-    score_map: device tensor [B, H, W] (or [B, H, W, 1]) float32 (`up`) or uint8 (the DenseCRF argmax); gt_masks: B host arrays [mh, mw].
-    Returns an int64 device tensor [B, 2] (written into `out` when given), plus with want_masks the predicted masks at the original
-    sizes (list of uint8 {0, 1} device tensors)."""
+def _mask_iu(score_map, gt_masks, thresh: float, want_masks: bool, out: torch.Tensor):
+    """mask_iu's work: (iu, packed predicted masks or None, descriptors, packed length, the uploaded ground truths on the device)."""
     m = score_map
     if not torch.is_tensor(m) or m.device.type != "cuda":
         raise ValueError("score_map must be a device tensor")
@@ -180,6 +184,15 @@ def mask_iu(score_map, gt_masks, thresh: float = 1e-9, want_masks: bool = False,
         dt = _lib.EVAL_F32 if m.dtype == torch.float32 else _lib.EVAL_U8
         _lib.call("cmpc_eval_mask_iu", m.data_ptr(), dt, B, H, W, float(thresh), gt.data_ptr(), nbytes, descs, iu.data_ptr(),
                   mo.data_ptr() if mo is not None else None, torch.cuda.current_stream(dev).cuda_stream)
+    return iu, mo, descs, nbytes, gt
+
+
+def mask_iu(score_map, gt_masks, thresh: float = 1e-9, want_masks: bool = False, out: torch.Tensor = None):
+    """(I, U) per sample of compute_mask_IU(resize_and_crop(score_map >= thresh, mh, mw), gt) on the device.
+    score_map: device tensor [B, H, W] (or [B, H, W, 1]) float32 (`up`) or uint8 (the DenseCRF argmax); gt_masks: B host arrays [mh, mw].
+    Returns an int64 device tensor [B, 2] (written into `out` when given), plus with want_masks the predicted masks at the original
+    sizes (list of uint8 {0, 1} device tensors)."""
+    iu, mo, descs, _, _ = _mask_iu(score_map, gt_masks, thresh, want_masks, out)
     if not want_masks:
         return iu
     return iu, [mo[d.offset: d.offset + d.h * d.w].view(d.h, d.w) for d in descs]
@@ -460,10 +473,15 @@ class Evaluator:
     metrics with dcrf).  dcrf_method: "exact" (one cmpc_dense_crf call per sample) or "lattice" (the batch's masks from one
     cmpc_dense_crf_lattice call, crf.py).  gv_norm: None leaves the model's gv_lang norm as it is (by default the batch-wide norm of the
     training graph: a sample's (I, U) then depends on its batch mates and on the pads of the last batch); "sample" gives every sample the
-    result of the reference's batch-1 `-m test` loop; either value is set around each forward pass and the model's own mode restored."""
+    result of the reference's batch-1 `-m test` loop; either value is set around each forward pass and the model's own mode restored.
+    visualize: None, or a callable fn(i, pics) -- the driver's `-v` switch (visualize_seg, trainval_model.py:306-330).  Every real sample
+    (never a pad) calls it exactly once, in sample order, with pics = {"im", "gt", "pred"} (and "pred_dcrf" with dcrf): uint8 [h, w, 3]
+    host arrays, valid during the call; gt and pred are cmpc_vis_overlay's pictures of the ground truth and of the masks
+    cmpc_eval_mask_iu writes, on the frames cmpc_eval_prep was given (visualize.EvaluatorPictures).  A batch's pictures are delivered
+    once the next batch is enqueued, or by result() / per_sample(); the metrics are the same integers with and without the hook."""
 
     def __init__(self, model, thresholds: Sequence[float] = (.5, .6, .7, .8, .9), dcrf: bool = False, score_thresh: float = 1e-9,
-                 dcrf_method: str = "exact", gv_norm: Optional[str] = None):
+                 dcrf_method: str = "exact", gv_norm: Optional[str] = None, visualize=None):
         _check_model(model)
         self.gv_norm = check_gv_norm(gv_norm)
         self.model, self.thresholds, self.dcrf, self.score_thresh = model, tuple(thresholds), bool(dcrf), float(score_thresh)
@@ -475,6 +493,12 @@ class Evaluator:
         self.n = 0
         self.iu = torch.zeros(64, 2, dtype=torch.int64, device=model.device)
         self.iu_crf = torch.zeros(64, 2, dtype=torch.int64, device=model.device) if self.dcrf else None
+        self.pictures = None
+        if visualize is not None:
+            if not callable(visualize):
+                raise ValueError("Evaluator: visualize must be None or a callable fn(i, pics)")
+            from . import visualize as VIS
+            self.pictures = VIS.EvaluatorPictures(visualize, model.device)
 
     def add(self, ids, seq_len, image, gt_mask):
         self.queue.append((np.asarray(ids, dtype=np.int32).reshape(-1), int(seq_len), image, gt_mask))
@@ -498,12 +522,19 @@ class Evaluator:
         ids = np.stack([s[0] for s in q])
         sl = np.array([s[1] for s in q], dtype=np.int32)
         with torch.cuda.device(m.device):
-            feed, proc = prepare_images([s[2] for s in q], self.H, self.W, m.device)
+            feed, proc, src, src_descs, src_bytes = _prepare_images([s[2] for s in q], self.H, self.W, m.device)
             with gv_norm_scope(m, self.gv_norm):
                 out = m.forward(ids, feed, sl)
             gts = [s[3] for s in q[:n]]
             self._grow(self.n + n)
-            mask_iu(out["up"][:n].float(), gts, self.score_thresh, out=self.iu[self.n: self.n + n])
+            pic = self.pictures
+            if pic is None:
+                mask_iu(out["up"][:n].float(), gts, self.score_thresh, out=self.iu[self.n: self.n + n])
+            else:
+                _, mo, descs, nbytes, gt_dev = _mask_iu(out["up"][:n].float(), gts, self.score_thresh, True, self.iu[self.n: self.n + n])
+                pic.begin(self.n, [s[2] for s in q[:n]], src, src_descs, src_bytes, descs, nbytes)
+                pic.overlay("gt", gt_dev)
+                pic.overlay("pred", mo)
             if self.dcrf:
                 from . import crf
                 sigm = out["sigm"].float()
@@ -511,19 +542,29 @@ class Evaluator:
                     crf_masks = crf.dense_crf_batch(sigm[:n].reshape(n, self.H, self.W), proc[:n], device=m.device, method="lattice")
                 else:
                     crf_masks = torch.stack([crf.dense_crf_mask(sigm[b].reshape(self.H, self.W), proc[b], device=m.device) for b in range(n)])
-                mask_iu(crf_masks, gts, 0.5, out=self.iu_crf[self.n: self.n + n])
+                if pic is None:
+                    mask_iu(crf_masks, gts, 0.5, out=self.iu_crf[self.n: self.n + n])
+                else:
+                    pic.overlay("pred_dcrf", _mask_iu(crf_masks, gts, 0.5, True, self.iu_crf[self.n: self.n + n])[1])
+            if pic is not None:
+                pic.end()
         self.n += n
 
     def _metrics(self, iu: np.ndarray) -> Dict[str, float]:
         return _metrics(iu, self.thresholds)
 
+    def _flush(self):
+        self._run()
+        if self.pictures is not None:
+            self.pictures.flush()
+
     def per_sample(self) -> np.ndarray:
         """(I, U) of every sample added so far (flushes the partial batch), int64 [n, 2]."""
-        self._run()
+        self._flush()
         return self.iu[: self.n].cpu().numpy()
 
     def result(self) -> Dict[str, float]:
-        self._run()
+        self._flush()
         if self.n == 0:
             raise ValueError("Evaluator.result: no samples")
         iu = self.iu[: self.n].cpu().numpy()

@@ -662,6 +662,43 @@ int cmpc_mask_jf_workspace(const cmpc_jf_desc* descs_host, int B, int64_t* bytes
 int cmpc_mask_jf(const unsigned char* pred, int64_t pred_bytes, const unsigned char* gt, int64_t gt_bytes,
                  const cmpc_jf_desc* descs_host, int B, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- The drivers' pictures (the `-v` switch of trainval_model.py:306-330 and CMPC_video/trainval_video.py, the panels of
+ *      test_visualize_fusion*.py:283-304 and test_visualize_graph.py:267-274) rendered on the device.  Packed buffers are described by
+ *      cmpc_eval_desc (offset, h, w, c; the geometry fields count only where stated).  Descriptors are HOST memory, validated before
+ *      anything is launched and passed by value; B in 1..CMPC_EVAL_MAX_BATCH; no allocation or synchronisation; each call writes the
+ *      bytes of its outputs and nothing else (bytes between packed samples are not touched).  Parity with matplotlib's own image
+ *      pipeline is unpinned: imshow resamples to screen pixels; these index the arrays' own pixels (csrc/ops_vis.hip states the rules,
+ *      tests/vis_ref.py repeats them in NumPy). ------------------------------------------------------------------------------------ */
+#define CMPC_VIS_PRED 0              /* (im0 >> 1) + 100 m, im1 >> 1, im2 >> 1: (im / 2; [:, :, 0] += predicts * 100).astype('uint8') */
+#define CMPC_VIS_GT 1                /* (170 m, 0, 170 (1 - m)) */
+#define CMPC_VIS_SIGMOID 1           /* cmpc_vis_heat flags: s = 1 / (1 + exp(-x)) in float32 before resampling */
+#define CMPC_VIS_AUTO 2              /*                      (lo, hi) = the sample's own min and max (imshow's autoscale) */
+/* out [h, w, 3] uint8 per sample from a uint8 frame [h, w, c] (c 1 or 3; a grey frame is tiled to three channels) and a uint8 mask
+ * [h, w] of the same size, m = mask != 0 (the package's "resampled value > 0" mask, cmpc_eval_mask_out).  CMPC_VIS_GT reads no frame:
+ * frames and frame_descs_host may be NULL.  The three descriptor arrays give each sample's offset and size in its buffer. */
+int cmpc_vis_overlay(int kind, const unsigned char* frames, int64_t frame_bytes, const cmpc_eval_desc* frame_descs_host,
+                     const unsigned char* masks, int64_t mask_bytes, const cmpc_eval_desc* mask_descs_host, int B,
+                     unsigned char* out, int64_t out_bytes, const cmpc_eval_desc* out_descs_host, void* stream);
+/* A colour-mapped map.  v = the float64 value of hostutil.resize_and_crop(s, d.h, d.w) of the float32 map [B, H, W] (s = map, or its
+ * float32 sigmoid with CMPC_VIS_SIGMOID), SciPy's arithmetic operation for operation as in cmpc_eval_prep (Gaussian radius <= 63);
+ * idx = clip(floor((v - lo) / (hi - lo) * 256), 0, 255) in float64, 0 when hi == lo; (lo, hi) = (vmin, vmax), vmin < vmax, or with
+ * CMPC_VIS_AUTO the min and max of v over the sample's outputs (exact and order-independent: reruns are bit-identical).  descs_host as
+ * for cmpc_eval_mask_out (resize_and_crop_geometry(H, W, d.h, d.w); offsets into idx_out).  Outputs, either or both: idx_out, packed
+ * uint8 [h, w] index planes; rgb_out, packed [h, w, 3] planes = lut[idx] at rgb_descs_host's offsets (lut: device [256][3] uint8).
+ * range_out: NULL or device float64 [B][2] receiving the (lo, hi) used.  ws: device scratch of cmpc_vis_heat_workspace's size, 8-byte
+ * aligned (CMPC_VIS_AUTO only; otherwise it may be NULL).  Maps must be finite; this is not checked. */
+int cmpc_vis_heat_workspace(int B, int flags, int64_t* bytes);
+int cmpc_vis_heat(const float* map, int B, int H, int W, const cmpc_eval_desc* descs_host, int flags, double vmin, double vmax,
+                  const unsigned char* lut, unsigned char* idx_out, int64_t idx_bytes, unsigned char* rgb_out, int64_t rgb_bytes,
+                  const cmpc_eval_desc* rgb_descs_host, double* range_out, void* ws, int64_t ws_bytes, void* stream);
+/* One RGB sheet per sample of the word panels of gw [B, N, ld] float32 (the gw_v_<level> fetch, ld = Tp, N = gh * gwd): panel t is
+ * gw[b, :, t] as (gh, gwd), indexed by cmpc_vis_heat's rule with its own min and max (float32 widened to float64; a constant panel is
+ * index 0), every pixel repeated zoom x zoom times.  rows = ceil(max_words / cols) rows of cols panels, `gap` pixels between panels:
+ * out [B, rows gh zoom + (rows - 1) gap, cols gwd zoom + (cols - 1) gap, 3] uint8.  Gaps and panels t >= n_words_host[b] are white.
+ * n_words_host[b] in 0..min(ld, max_words), max_words in 1..32, zoom >= 1, cols >= 1, gap >= 0.  No resampling: results are exact. */
+int cmpc_vis_words(const float* gw, int B, int gh, int gwd, int ld, const int* n_words_host, int max_words, int zoom, int cols, int gap,
+                   const unsigned char* lut, unsigned char* out, int64_t out_bytes, void* stream);
+
 /* Host utility (no GPU): CRC-32C of `n` bytes, continuing from `crc` (0 to start) -- the checksum of TensorFlow's tensor-bundle
  * checkpoints (trainval_model.py:46-63 restores / saves them; cmpc-refseg_amd/tf_bundle.py reads and writes the format). */
 uint32_t cmpc_crc32c(uint32_t crc, const void* data, size_t n);
