@@ -10,7 +10,11 @@
 
 namespace {
 
-constexpr int MAXR = 63;                 // Gaussian radius limit (shrink factors up to ~32)
+// Gaussian radius limit: int(4 sigma + 0.5) <= 63, i.e. shrink factors below 32.75 per axis.  Grey images and masks go that far; a colour
+// source is refused earlier, by eval_prep's LDS footprint (at radii 63 / 63 even the 1 x 1 tile needs ~70 KB): 720 x 1280 x 3 into 23 x 41
+// (radii 61 / 60) is refused, the same source in grey is not, and a square colour source fits up to radius 59 there
+// (tests/test_gpu_resample_edges.py).
+constexpr int MAXR = 63;
 
 struct SampleGeo {                       // host-derived per-sample constants (passed by value)
     double zy, zx;                       // source / resized, float64 (ndimage.zoom's factors)
