@@ -143,6 +143,9 @@ class JfDesc(C.Structure):
 
 
 JF_MAX_RADIUS = 128      # CMPC_JF_MAX_RADIUS
+POOL_SOFT, POOL_HARD = 0, 1               # CMPC_POOL_* modes of cmpc_mask_pool
+POOL_MODES = {"soft": POOL_SOFT, "hard": POOL_HARD}
+POOL_CHUNK = 64                           # CMPC_POOL_CHUNK: positions per partial row
 VIS_PRED, VIS_GT = 0, 1                   # CMPC_VIS_* kinds of cmpc_vis_overlay
 VIS_SIGMOID, VIS_AUTO = 1, 2              # CMPC_VIS_* flags of cmpc_vis_heat
 
@@ -266,6 +269,9 @@ SIGNATURES = {
     "cmpc_train_accuracy": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "cmpc_mask_jf_workspace": [C.POINTER(JfDesc), _I, C.POINTER(_L)],
     "cmpc_mask_jf": [_P, _L, _P, _L, C.POINTER(JfDesc), _I, _P, _P, _L, _P],
+    "cmpc_mask_pool_workspace": [_I, _I, _I, _I, C.POINTER(_L)],
+    "cmpc_mask_pool": [_I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _L, _P],
+    "cmpc_level_agree": [_P, _P, _I, _I, _I, _F, _P, _P],
     "cmpc_vis_overlay": [_I, _P, _L, C.POINTER(EvalDesc), _P, _L, C.POINTER(EvalDesc), _I, _P, _L, C.POINTER(EvalDesc), _P],
     "cmpc_vis_heat_workspace": [_I, _I, C.POINTER(_L)],
     "cmpc_vis_heat": [_P, _I, _I, _I, C.POINTER(EvalDesc), _I, C.c_double, C.c_double, _P, _P, _L, _P, _L, C.POINTER(EvalDesc), _P, _P, _L, _P],

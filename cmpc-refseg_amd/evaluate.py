@@ -385,6 +385,146 @@ def mask_jf(preds, gts, bound_th: float = 0.008, device="cuda:0") -> np.ndarray:
         return counts.cpu().numpy()
 
 
+# ---- pivot frames: cmpc_mask_pool and cmpc_level_agree (include/cmpc.h; hostutil.find_pivot_frames / PivotLog use what they give) ------
+_POOL_DT = {torch.float32: _lib.DT_F32, torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16}
+
+
+def check_pool_mode(mode: str) -> str:
+    if mode not in _lib.POOL_MODES:
+        raise ValueError("describe weights must be 'soft' or 'hard', got %r" % (mode,))
+    return mode
+
+
+def agree_logit(threshold: float) -> float:
+    """The logit of a probability threshold, log(t / (1 - t)) in float64 rounded to float32: sigmoid(x) > t as x > logit."""
+    t = float(threshold)
+    if not 0.0 < t < 1.0:
+        raise ValueError("threshold must be a probability in (0, 1), got %r" % (threshold,))
+    return float(np.float32(np.log(t / (1.0 - t))))
+
+
+def pool_workspace(n: int, h: int, w: int, C: int) -> int:
+    """cmpc_mask_pool_workspace: n * ceil(h * w / POOL_CHUNK) partial rows of C + 8 floats, in bytes."""
+    import ctypes
+    out = ctypes.c_int64()
+    _lib.call("cmpc_mask_pool_workspace", int(n), int(h), int(w), int(C), ctypes.byref(out))
+    return out.value
+
+
+class _PoolDevice:
+    """The device half of describing, shared by mask_pool / level_agree and the two segmenters: both kernels read their inputs where
+    they lie and write where they are told, on the current stream.  The workspace grows only when a call needs more than any before
+    it (reserve() ahead of the steady state)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.ws = None
+        self._need: Dict[Tuple[int, int, int, int], int] = {}     # sizes asked for so far -> workspace bytes (one library call per size)
+
+    def reserve(self, n: int, h: int, w: int, C: int) -> int:
+        key = (int(n), int(h), int(w), int(C))
+        need = self._need.get(key)
+        if need is None:
+            need = self._need[key] = pool_workspace(*key)
+        if self.ws is None or self.ws.numel() * 4 < need:
+            with torch.cuda.device(self.device):
+                self.ws = torch.empty(max(need // 4, 1 << 16), dtype=torch.float32, device=self.device)
+        return need
+
+    def pool(self, feat: torch.Tensor, n: int, score_ptr: int, sH: int, sW: int, mode: str, threshold: float, desc_ptr: int, area_ptr: int):
+        """feat: [>= n, h, w, C] whose results are contiguous taps (any stride between them); score: float32 [n, sH, sW] at score_ptr."""
+        h, w, C = (int(x) for x in feat.shape[1:])
+        self.reserve(n, h, w, C)
+        stride = int(feat.stride(0)) if feat.shape[0] > 1 else h * w * C
+        _lib.call("cmpc_mask_pool", _POOL_DT[feat.dtype], feat.data_ptr(), stride, score_ptr, int(sH), int(sW), int(n), h, w, C,
+                  _lib.POOL_MODES[mode], float(threshold), desc_ptr, area_ptr, self.ws.data_ptr(), self.ws.numel() * 4,
+                  torch.cuda.current_stream(self.device).cuda_stream)
+
+    def agree(self, a_ptr: int, b_ptr: int, n: int, h: int, w: int, logit: float, counts_ptr: int):
+        _lib.call("cmpc_level_agree", a_ptr, b_ptr, int(n), int(h), int(w), float(logit), counts_ptr,
+                  torch.cuda.current_stream(self.device).cuda_stream)
+
+
+_POOL_DEVICE: Dict[str, _PoolDevice] = {}
+
+
+def _pool_device(dev) -> _PoolDevice:
+    key = str(dev)
+    if key not in _POOL_DEVICE:
+        _POOL_DEVICE[key] = _PoolDevice(dev)
+    return _POOL_DEVICE[key]
+
+
+def _check_tap(feat):
+    if not torch.is_tensor(feat) or feat.device.type != "cuda" or feat.dtype not in _POOL_DT or feat.dim() != 4 or feat.numel() == 0:
+        raise ValueError("feat must be a float32, float16 or bfloat16 device tensor [n, h, w, C]")
+    n, h, w, C = feat.shape
+    if C % 8:
+        raise ValueError("feat: C = %d is not a multiple of 8" % C)
+    if feat.stride()[1:] != (w * C, C, 1) or (n > 1 and (feat.stride(0) < h * w * C or feat.stride(0) % 8)) or feat.data_ptr() % 16:
+        raise ValueError("feat: each result must be a contiguous, 16-byte aligned [h, w, C] tap (strides %s)" % (tuple(feat.stride()),))
+
+
+def mask_pool(feat, score, mode: str = "soft", threshold: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """cmpc_mask_pool on device tensors: desc[i, c] = sum_{y, x} wgt_i[y, x] * feat[i, y, x, c] and area[i] = sum wgt_i, with wgt_i the
+    point sample score[i, y * (sH / h), x * (sW / w)] (mode "soft") or that float32 >= threshold ? 1 : 0 ("hard").  feat: [n, h, w, C]
+    float32 / float16 / bfloat16, each result a contiguous tap (a slice or a strided selection of a batch is read in place); score:
+    float32 [n, sH, sW] or [n, sH, sW, 1] on the same device, sH % h == 0 and sW % w == 0.  Runs in chunks of MAX_BATCH on the current
+    stream, nothing synchronises.  Returns float32 device tensors (desc [n, C], area [n]).  The partial rows live in ONE workspace per
+    device, shared by every call of this function on that device: calls must follow one another on one stream; calls from several host
+    threads, or on several streams that may run side by side, would share the rows and must be serialised by the caller (the segmenters
+    own a workspace each)."""
+    check_pool_mode(mode)
+    _check_tap(feat)
+    if not torch.is_tensor(score) or score.device != feat.device or score.dtype != torch.float32:
+        raise ValueError("score must be a float32 tensor on feat's device")
+    if score.dim() == 4 and score.shape[3] == 1:
+        score = score[..., 0]
+    n, h, w, C = feat.shape
+    if score.dim() != 3 or score.shape[0] != n or score.shape[1] % h or score.shape[2] % w or score.shape[1] < h or score.shape[2] < w:
+        raise ValueError("score %s against feat %s: [n, sH, sW] with sH, sW multiples of the tap grid" % (tuple(score.shape), tuple(feat.shape)))
+    score = score.contiguous()
+    dev = feat.device
+    pd = _pool_device(dev)
+    with torch.cuda.device(dev):
+        desc = torch.empty(n, C, dtype=torch.float32, device=dev)
+        area = torch.empty(n, dtype=torch.float32, device=dev)
+        for s in range(0, n, MAX_BATCH):
+            k = min(MAX_BATCH, n - s)
+            pd.pool(feat[s: s + k], k, score[s: s + k].data_ptr(), score.shape[1], score.shape[2], mode, threshold,
+                    desc[s: s + k].data_ptr(), area[s: s + k].data_ptr())
+    return desc, area
+
+
+def level_agree(a, b, threshold: float = 0.2) -> torch.Tensor:
+    """cmpc_level_agree on device tensors: int64 [n, 2] = (I, U), the sizes of (sigmoid(a) > threshold) & (sigmoid(b) > threshold) and of
+    their union -- loss.iou_with_threshold (util/loss.py:51-68) as exact integers; hostutil.consistency gives I / U.  a, b: float32 logit
+    maps [n, h, w] or [n, h, w, 1] of one shape on one device.  The probability threshold becomes the logit agree_logit(threshold) and
+    the maps are compared with it as they are (no exp).  Chunks of MAX_BATCH on the current stream, nothing synchronises."""
+    logit = agree_logit(threshold)
+    ts = []
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != torch.float32:
+            raise ValueError("%s must be a float32 device tensor" % name)
+        if t.dim() == 4 and t.shape[3] == 1:
+            t = t[..., 0]
+        if t.dim() != 3 or t.numel() == 0:
+            raise ValueError("%s must be [n, h, w] or [n, h, w, 1], got %s" % (name, tuple(t.shape)))
+        ts.append(t.contiguous())
+    a, b = ts
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("a %s on %s and b %s on %s: one shape and one device" % (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    n, h, w = a.shape
+    dev = a.device
+    pd = _pool_device(dev)
+    with torch.cuda.device(dev):
+        counts = torch.empty(n, 2, dtype=torch.int64, device=dev)
+        for s in range(0, n, MAX_BATCH):
+            k = min(MAX_BATCH, n - s)
+            pd.agree(a[s: s + k].data_ptr(), b[s: s + k].data_ptr(), k, h, w, logit, counts[s: s + k].data_ptr())
+    return counts
+
+
 def unpack_masks(buf, descs) -> list:
     """The [h, w] views of a packed mask buffer (device tensor or NumPy array) at its descriptors' offsets."""
     if torch.is_tensor(buf):

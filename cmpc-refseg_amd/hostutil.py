@@ -418,3 +418,99 @@ class JFEval:
         out["J&F"] = (out["J_mean"] + out["F_mean"]) / 2
         out["sequences"], out["frames"], out["per_sequence"] = len(per), sum(p["frames"] for p in per.values()), per
         return out
+
+
+# ---- pivot frames (test.py:150-181) and the per-frame consistency of two levels (test.py:289,301-302; util/loss.py:51-68) ---------------
+# find_pivot_frames restates the reference's function with its two crashes repaired -- its row normalisation broadcasts [F, C] / [F],
+# and `avail_frame[a:b] = False` assigns a scalar to a list slice -- and nothing else changed.  The reference's function cannot run, so
+# parity against it is UNPINNED.  The descriptors and counts come from cmpc_mask_pool / cmpc_level_agree (evaluate.mask_pool,
+# evaluate.level_agree, the segmenters' describe=).
+def find_pivot_frames(descriptors, num_propagate: int = 2, nearest_first: bool = False) -> List[int]:
+    """The frames a mask propagator would start from, as 0-based row indices of `descriptors` [F, C] (one global feature per frame).
+    Rows are normalised in float64 (a zero row stays zero: its similarity to everything is 0); S = the cosine similarities;
+    first = argmax of S.sum(0) (first occurrence); the frames are tried in the order of a stable argsort of S[first] -- ascending as the
+    reference writes it, so the frame LEAST like `first` is tried first and `first` itself last; nearest_first=True tries them in
+    the descending order (a stable argsort of -S[first]) -- and a frame is taken if it is still available, after which the frames
+    [f - num_propagate, f + num_propagate] are not.  No two pivots lie within num_propagate of each other and every frame lies
+    within num_propagate of a pivot."""
+    d = np.asarray(descriptors, dtype=np.float64)
+    if d.ndim != 2 or d.shape[0] < 1:
+        raise ValueError("find_pivot_frames: descriptors must be [F, C] with F >= 1, got %s" % (d.shape,))
+    p = int(num_propagate)
+    if p < 0:
+        raise ValueError("find_pivot_frames: num_propagate %r < 0" % (num_propagate,))
+    F = d.shape[0]
+    norm = np.linalg.norm(d, axis=1, keepdims=True)
+    dn = np.divide(d, norm, out=np.zeros_like(d), where=norm > 0)
+    S = dn @ dn.T
+    first = int(np.argmax(S.sum(0)))
+    to_first = S[first]
+    order = np.argsort(-to_first if nearest_first else to_first, kind="stable")
+    avail, out = [True] * F, []
+    for f in order:
+        f = int(f)
+        if avail[f]:
+            out.append(f)
+            lo, hi = max(f - p, 0), min(f + p + 1, F)
+            avail[lo:hi] = [False] * (hi - lo)
+    return out
+
+
+def consistency(I, U) -> float:
+    """loss.iou_with_threshold from its two counts: I / U, NaN when U == 0 (0 / 0 there; test.py:301 guards with math.isnan)."""
+    I, U = int(I), int(U)
+    return float("nan") if U == 0 else I / U
+
+
+class PivotLog:
+    """What the segmenters' describe= collects, per sequence (one (video, expression) pair):
+
+        log = PivotLog(); log.add(seq, frame, desc, area, (I, U)) ...; log.pivots(seq); log.inconsistent(); log.meta()
+
+    desc: the frame's float32 descriptor [C] (cmpc_mask_pool); area: the sum of its weights; (I, U): cmpc_level_agree's counts."""
+
+    def __init__(self):
+        self.seqs: Dict[object, Dict[int, Tuple[np.ndarray, float, float]]] = {}
+
+    def add(self, seq, frame: int, desc, area, iu):
+        frames = self.seqs.setdefault(seq, {})
+        if frame in frames:
+            raise ValueError("PivotLog.add: sequence %r already holds frame %r" % (seq, frame))
+        I, U = (int(v) for v in np.asarray(iu).reshape(2))
+        frames[frame] = (np.array(desc, dtype=np.float32).reshape(-1), float(area), consistency(I, U))
+
+    def __len__(self) -> int:
+        return sum(len(f) for f in self.seqs.values())
+
+    def _frames(self, seq) -> Dict[int, Tuple[np.ndarray, float, float]]:
+        if seq not in self.seqs:
+            raise KeyError("PivotLog: no sequence %r" % (seq,))
+        return self.seqs[seq]
+
+    def descriptors(self, seq) -> Tuple[np.ndarray, List[int]]:
+        """([F, C] float32 in frame order, the frame ids)."""
+        frames = self._frames(seq)
+        ids = sorted(frames)
+        return np.stack([frames[f][0] for f in ids]), ids
+
+    def areas(self, seq) -> np.ndarray:
+        frames = self._frames(seq)
+        return np.array([frames[f][1] for f in sorted(frames)], dtype=np.float64)
+
+    def consistencies(self, seq) -> np.ndarray:
+        """I / U per frame in frame order, NaN where both levels are empty."""
+        frames = self._frames(seq)
+        return np.array([frames[f][2] for f in sorted(frames)], dtype=np.float64)
+
+    def pivots(self, seq, num_propagate: int = 2, nearest_first: bool = False) -> List[int]:
+        """find_pivot_frames on the sequence's descriptors, as frame ids."""
+        d, ids = self.descriptors(seq)
+        return [ids[i] for i in find_pivot_frames(d, num_propagate, nearest_first)]
+
+    def inconsistent(self, below: float = 0.3) -> List[Tuple[object, int]]:
+        """(seq, frame) of every frame whose consistency is below `below` (test.py:301-302); never a NaN one."""
+        return [(seq, f) for seq, frames in self.seqs.items() for f in sorted(frames) if frames[f][2] < below]
+
+    def meta(self, num_propagate: int = 2, nearest_first: bool = False) -> Dict[object, List[int]]:
+        """{seq: pivots}: the content of test.py's meta_pivot_frames."""
+        return {seq: self.pivots(seq, num_propagate, nearest_first) for seq in self.seqs}

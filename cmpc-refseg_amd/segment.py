@@ -37,7 +37,8 @@ from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, hostutil as HU
-from .evaluate import JF_COUNTS, MAX_BATCH, JfPlan, _check_dcrf_method, _images_u8, check_gv_norm, gv_norm_scope, plan_masks, plan_prep
+from .evaluate import (JF_COUNTS, MAX_BATCH, JfPlan, _check_dcrf_method, _images_u8, agree_logit, check_gv_norm, check_pool_mode, gv_norm_scope,
+                       plan_masks, plan_prep)
 
 
 def half_size(h: int, w: int) -> Tuple[int, int]:
@@ -119,18 +120,90 @@ def _enqueue_scoring(stage, plan: JfPlan, nbytes: int) -> int:
     return scored_bytes(nbytes, plan.n)
 
 
+# ---- describe=: a descriptor, its area and the agreement of two levels per result, for hostutil.PivotLog --------------------------------
+DESCRIBE_LEVELS = ("c3", "c4", "c5")           # the backbone taps in the order model.features returns them
+AGREE_THRESHOLD = 0.2                          # CMPCv4_model.py:146: iou_with_threshold(sigmoid(score_c4), sigmoid(score_c5), 0.2)
+
+
+def check_describe(model, describe: Optional[str], weights: str) -> Optional[int]:
+    """describe -> the index of that tap in model.features' result (None: no describing).  Raises ValueError for an unknown level or
+    weights, and for "c3" on the CMPCv5 models, whose first tap is c2 at another grid."""
+    check_pool_mode(weights)
+    if describe is None:
+        return None
+    if describe not in DESCRIBE_LEVELS:
+        raise ValueError("describe must be None, 'c3', 'c4' or 'c5', got %r" % (describe,))
+    if describe == "c3" and getattr(model, "v5", False):
+        raise ValueError("describe='c3': the CMPCv5 models' first tap is c2, at another grid than c4 and c5; use 'c4' or 'c5'")
+    return DESCRIBE_LEVELS.index(describe)
+
+
+class DescribePlan:
+    """Where the describe tail of a ring slot with n results lies, every part 4-byte and the counts 8-byte aligned: int64 counts
+    [n, 2] (I, U) at `off` (8-aligned: behind the masks, and behind the J / F counts when the slot is scored), float32 descriptors
+    [n, C] behind them, float32 areas [n] behind those; `end`: the bytes the slot's one copy then carries."""
+    __slots__ = ("n", "C", "off", "desc_off", "area_off", "end")
+
+    def __init__(self, n: int, C: int, off: int):
+        if off % 8:
+            raise ValueError("DescribePlan: offset %d is not 8-byte aligned" % off)
+        self.n, self.C, self.off = int(n), int(C), int(off)
+        self.desc_off = self.off + 16 * self.n
+        self.area_off = self.desc_off + 4 * self.n * self.C
+        self.end = self.area_off + 4 * self.n
+
+
+def plan_describe(nbytes: int, n_scored: int, n: int, C: int) -> DescribePlan:
+    """The tail of a slot that holds `nbytes` of packed masks, the J / F counts of n_scored of them and n described results."""
+    return DescribePlan(n, C, scored_bytes(nbytes, n_scored))
+
+
+def slot_describe(host: np.ndarray, plan: DescribePlan) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(int64 counts [n, 2], float32 descriptors [n, C], float32 areas [n]) at the tail of a pinned slot (views)."""
+    return (host[plan.off: plan.desc_off].view(np.int64).reshape(plan.n, 2),
+            host[plan.desc_off: plan.area_off].view(np.float32).reshape(plan.n, plan.C),
+            host[plan.area_off: plan.end].view(np.float32))
+
+
+def _tap_channels(model, level: int) -> int:
+    cfg = model.cfg
+    return int((cfg.c3_dim, cfg.c4_dim, cfg.vf_dim)[level])
+
+
+def _check_describe_grid(model, level: int):
+    cfg = model.cfg
+    if model.H % cfg.vf_h or model.W % cfg.vf_w or _tap_channels(model, level) % 8:
+        raise ValueError("describe: a %d x %d score map over a %d x %d tap of %d channels: the map must be a multiple of the tap grid and "
+                         "the channels a multiple of 8" % (model.H, model.W, cfg.vf_h, cfg.vf_w, _tap_channels(model, level)))
+
+
+def _enqueue_describe(stage, tap, i0: int, sigm_ptr: int, a, b, plan: DescribePlan, row: int, n: int):
+    """The device half both stages share: cmpc_mask_pool on results i0 .. i0 + n - 1 of `tap` weighted by the n float32 [H, W] maps at
+    sigm_ptr, cmpc_level_agree on the n logit maps a and b, into rows row .. row + n - 1 of the plan's tail in stage.mask_dev."""
+    m, base = stage.model, stage.mask_dev.data_ptr()
+    mode, level = stage.describe
+    stage.pooler.pool(tap[i0:], n, sigm_ptr, m.H, m.W, mode, stage.threshold_pool, base + plan.desc_off + 4 * plan.C * row,
+                      base + plan.area_off + 4 * row)
+    stage.pooler.agree(a.data_ptr(), b.data_ptr(), n, int(a.shape[1]), int(a.shape[2]), stage.agree_logit, base + plan.off + 16 * row)
+
+
 class _DeviceStage:
     """The device half of FrameSegmenter.  All buffers are allocated once (the pinned ring and the device mask buffer grow only when a
     batch needs more bytes than any before it): two feed / proc_im sets that alternate with the frame batches, one device mask buffer,
     `nslots` pinned host buffers with an event each.  Everything is enqueued on the caller's current stream."""
 
-    def __init__(self, model, nslots: int, threshold: float, value: int, dcrf: bool, dcrf_method: str):
+    def __init__(self, model, nslots: int, threshold: float, value: int, dcrf: bool, dcrf_method: str, describe=None):
         import torch
-        from .evaluate import _JfDevice, _Staging
+        from .evaluate import _JfDevice, _PoolDevice, _Staging
         self.torch = torch
         self.model, self.threshold, self.value, self.dcrf, self.dcrf_method = model, threshold, value, dcrf, dcrf_method
         self.dev = model.device
         B, H, W = model.batch_size, model.H, model.W
+        self.describe = describe                       # (weights, index of the tap) or None
+        if describe is not None:
+            _check_describe_grid(model, describe[1])
+            self.pooler, self.threshold_pool, self.agree_logit = _PoolDevice(self.dev), threshold, agree_logit(AGREE_THRESHOLD)
+            self.pooler.reserve(B, model.cfg.vf_h, model.cfg.vf_w, self.describe_channels())
         with torch.cuda.device(self.dev):
             self.staging = _Staging(self.dev)
             self.feed = [torch.empty(B, H, W, 3, dtype=torch.float32, device=self.dev) for _ in range(2)]
@@ -157,6 +230,9 @@ class _DeviceStage:
             if o is not None:
                 h[: o.numel()].copy_(o)
 
+    def describe_channels(self) -> int:
+        return _tap_channels(self.model, self.describe[1])
+
     def set_expressions(self, exprs: Sequence[Tuple[np.ndarray, int]]):
         torch, B = self.torch, self.model.batch_size
         with torch.cuda.device(self.dev):
@@ -176,9 +252,10 @@ class _DeviceStage:
             feats, done = m.features_async(feed)
         return feats, done, feed, proc
 
-    def segment(self, token, e: int, descs, nbytes: int, slot: int, jf: Optional[JfPlan] = None):
+    def segment(self, token, e: int, descs, nbytes: int, slot: int, jf: Optional[JfPlan] = None, describe: Optional[DescribePlan] = None):
         """Head of expression e on the batch's taps, the masks of its first len(descs) frames into ring slot `slot`; with `jf`, their
-        J / F counts behind them."""
+        J / F counts behind them; with `describe`, their descriptors (the batch's tap weighted by the head's sigm, with DenseCRF too:
+        the descriptor describes the network's own answer), areas and level-agreement counts behind those."""
         torch, m = self.torch, self.model
         feats, done, feed, proc = token
         n = len(descs)
@@ -196,6 +273,9 @@ class _DeviceStage:
                       self.mask_dev.numel(), self.value, torch.cuda.current_stream(self.dev).cuda_stream)
             if jf is not None:
                 nbytes = _enqueue_scoring(self, jf, nbytes)
+            if describe is not None:
+                _enqueue_describe(self, feats[self.describe[1]], 0, sigm.data_ptr(), o["score_c4"], o["score_c5"], describe, 0, n)
+                nbytes = describe.end
             self.host[slot][:nbytes].copy_(self.mask_dev[:nbytes], non_blocking=True)
             self.events[slot].record(torch.cuda.current_stream(self.dev))
 
@@ -224,10 +304,19 @@ class FrameSegmenter:
     annotation, a mask at out_size(h, w), or an (annotation, key) pair for hostutil.object_mask; it is called once per pair, on the
     caller's thread, when that result is enqueued.  The counts travel with the masks and are added to `jf` (a hostutil.JFEval, kept
     as self.jf; a fresh one when none is passed) under sequence (seq, e) and frame f as the masks are handed out; the yielded
-    triples are the same with and without it."""
+    triples are the same with and without it.
+
+    describe="c3" | "c4" | "c5" also describes every result for the reference's pivot-frame step (test.py:150-181): behind each head
+    call cmpc_mask_pool pools that backbone tap weighted by the head's sigm (describe_weights="soft") or by sigm >= threshold
+    ("hard"), and cmpc_level_agree counts where the score_c4 and score_c5 levels agree at probability 0.2 (test.py:289).  Descriptor,
+    area and counts travel with the masks and reach `pivots` (run(..., pivots=), a hostutil.PivotLog kept as self.pivots; a fresh one
+    when none is passed) under sequence (seq, e) and frame f before the masks are yielded; the yielded triples are the same.  A log
+    holds a (sequence, frame) once: a second run() with the same `pivots` and the same `seq` raises ValueError from PivotLog.add when
+    its first result is handed out -- pass a fresh log or another seq."""
 
     def __init__(self, model, vocab=None, threshold: float = 0.5, out_size: Callable[[int, int], Tuple[int, int]] = half_size, value: int = 255,
-                 dcrf: bool = False, dcrf_method: str = "lattice", gv_norm: str = "sample", depth: int = 2, copy: bool = True, _stage=None):
+                 dcrf: bool = False, dcrf_method: str = "lattice", gv_norm: str = "sample", depth: int = 2, copy: bool = True, _stage=None,
+                 describe: Optional[str] = None, describe_weights: str = "soft"):
         if getattr(model, "video", False):
             raise ValueError("FrameSegmenter: the video model (CMPC_video_mm_tgraph_allvec) is not supported: it takes a clip per forward pass")
         if model.batch_size > MAX_BATCH:
@@ -243,7 +332,15 @@ class FrameSegmenter:
         self.B, self.T, self.H, self.W = model.batch_size, model.num_steps, model.H, model.W
         self.nslots = self.depth + 1
         self.jf, self.bound_th = None, 0.008
-        self.stage = _stage if _stage is not None else _DeviceStage(model, self.nslots, self.threshold, self.value, self.dcrf, self.dcrf_method)
+        self.describe, self.describe_weights, self.pivots = describe, describe_weights, None
+        level = check_describe(model, describe, describe_weights)
+        if _stage is not None:
+            self.stage = _stage
+        elif level is None:
+            self.stage = _DeviceStage(model, self.nslots, self.threshold, self.value, self.dcrf, self.dcrf_method)
+        else:
+            self.stage = _DeviceStage(model, self.nslots, self.threshold, self.value, self.dcrf, self.dcrf_method,
+                                      describe=(describe_weights, level))
 
     def _batches(self, frames: Iterable) -> Iterator[Tuple[int, List[np.ndarray]]]:
         """(index of the first frame, the validated frames) of every batch of B, read lazily."""
@@ -271,25 +368,32 @@ class FrameSegmenter:
         return descs, nbytes
 
     def run(self, frames: Iterable, expressions: Sequence, ground_truth: Optional[Callable] = None, jf: Optional[HU.JFEval] = None,
-            seq=None) -> Iterator[Tuple[int, int, np.ndarray]]:
+            seq=None, pivots: Optional[HU.PivotLog] = None) -> Iterator[Tuple[int, int, np.ndarray]]:
         exprs = [check_expression(i, ex, self.vocab, self.T) for i, ex in enumerate(expressions)]
         if not exprs:
             raise ValueError("FrameSegmenter.run: no expressions")
         if ground_truth is not None:
             self.jf = jf if jf is not None else HU.JFEval()
         st = self.stage
+        C = None                                   # channels of the described tap
+        if self.describe is not None:
+            self.pivots = pivots if pivots is not None else HU.PivotLog()
+            C = st.describe_channels()
         free = deque(range(self.nslots))
-        pending = deque()                          # (slot, e, first frame, descs, scoring plan) in enqueue order = yield order
+        pending = deque()                          # (slot, e, first frame, descs, scoring plan, describe plan) in enqueue order = yield order
 
         def hand_out(block: bool):
             """Yield the masks of the oldest result(s) whose event has completed (waiting for the oldest one if `block`)."""
             while pending and (block or st.done(pending[0][0])):
-                slot, e, first, descs, plan = pending.popleft()
+                slot, e, first, descs, plan, dplan = pending.popleft()
                 st.wait(slot)
                 host = st.view(slot)
                 if plan is not None:
                     for i, c in zip(plan.idx, slot_counts(host, plan)):
                         self.jf.add((seq, e), first + i, c)
+                if dplan is not None:
+                    for i, (iu, d, a) in enumerate(zip(*slot_describe(host, dplan))):
+                        self.pivots.add((seq, e), first + i, d, a, iu)
                 for i, d in enumerate(descs):
                     mk = host[d.offset: d.offset + d.h * d.w].reshape(d.h, d.w)
                     yield e, first + i, (mk.copy() if self.copy else mk)
@@ -306,7 +410,10 @@ class FrameSegmenter:
                     return None
                 first, ims = nxt
                 descs, nbytes = self._plan(first, ims)
-                st.reserve(nbytes if ground_truth is None else scored_bytes(nbytes, len(descs)))
+                if C is None:
+                    st.reserve(nbytes if ground_truth is None else scored_bytes(nbytes, len(descs)))
+                else:
+                    st.reserve(plan_describe(nbytes, 0 if ground_truth is None else len(descs), len(descs), C).end)
                 return first, descs, nbytes, st.begin(ims + [ims[0]] * (self.B - len(ims)))
 
             cur = begin_next()
@@ -319,15 +426,21 @@ class FrameSegmenter:
                     if not free:
                         yield from hand_out(True)
                     slot = free.popleft()
-                    if ground_truth is None:
-                        plan = None
-                        st.segment(token, e, descs, nbytes, slot)
-                    else:
+                    # three call shapes on purpose: a stage written before jf= or describe= existed (the fake stages of the older host
+                    # tests, a caller's own _stage) keeps working as long as the options it does not know stay off
+                    plan = dplan = None
+                    if ground_truth is not None:
                         gts = [(i, ground_truth(e, first + i)) for i in range(len(descs))]
                         plan = plan_scoring(descs, [(i, check_ground_truth(e, first + i, g, (descs[i].h, descs[i].w)))
                                                     for i, g in gts if g is not None], nbytes, self.bound_th)
+                    if C is not None:
+                        dplan = plan_describe(nbytes, 0 if plan is None else plan.n, len(descs), C)
+                        st.segment(token, e, descs, nbytes, slot, jf=plan, describe=dplan)
+                    elif ground_truth is not None:
                         st.segment(token, e, descs, nbytes, slot, jf=plan)
-                    pending.append((slot, e, first, descs, plan))
+                    else:
+                        st.segment(token, e, descs, nbytes, slot)
+                    pending.append((slot, e, first, descs, plan, dplan))
                     yield from hand_out(False)
                 cur = nxt
             while pending:
@@ -387,10 +500,10 @@ class _ClipStage:
     batch evicts among it), and the batch's event is recorded behind the scatter.  Gathers, heads, cmpc_eval_mask_out and the copies to
     the pinned ring run on the caller's stream; a gather waits for the event of the newest batch its clip reads."""
 
-    def __init__(self, model, ring: int, nslots: int, score: str, threshold: float, value: int, dcrf: bool, dcrf_method: str):
+    def __init__(self, model, ring: int, nslots: int, score: str, threshold: float, value: int, dcrf: bool, dcrf_method: str, describe=None):
         import ctypes
         import torch
-        from .evaluate import _JfDevice, _Staging
+        from .evaluate import _JfDevice, _PoolDevice, _Staging
         from .model import FRAME_IDX
         self.torch, self.C = torch, ctypes
         self.model, self.score, self.threshold, self.value, self.dcrf, self.dcrf_method = model, score, threshold, value, dcrf, dcrf_method
@@ -410,6 +523,16 @@ class _ClipStage:
             self.batch_ev = [torch.cuda.Event() for _ in range(ring // B + 2)]
             self.events = [torch.cuda.Event() for _ in range(nslots)]
         self.scorer = _JfDevice(self.dev)
+        self.describe = describe                       # (weights, index of the tap) or None
+        if describe is not None:
+            _check_describe_grid(model, describe[1])
+            if model.frames // 2 not in FRAME_IDX:
+                raise ValueError("describe: clip position %d (the frame itself) is not among the sampled positions %s" % (model.frames // 2, FRAME_IDX))
+            self.own = FRAME_IDX.index(model.frames // 2)      # where frame f itself lies among its gathered taps
+            # "hard" weights are sigm >= threshold: the run's own threshold when it thresholds sigm, else 0.5 (up >= 1e-9 is a logit >= 0)
+            self.pooler, self.threshold_pool = _PoolDevice(self.dev), (threshold if score == "sigm" else 0.5)
+            self.agree_logit = agree_logit(AGREE_THRESHOLD)
+            self.pooler.reserve(1, model.cfg.vf_h, model.cfg.vf_w, self.describe_channels())
         self.bytes = [t[0].numel() * t.element_size() for t in taps]
         for b in self.bytes:
             if b % 16:
@@ -439,6 +562,9 @@ class _ClipStage:
         for o, h in zip(old, self.host):               # results not handed out yet move with their slot
             if o is not None:
                 h[: o.numel()].copy_(o)
+
+    def describe_channels(self) -> int:
+        return _tap_channels(self.model, self.describe[1])
 
     def set_expressions(self, exprs: Sequence[Tuple[np.ndarray, int]]):
         torch = self.torch
@@ -482,12 +608,16 @@ class _ClipStage:
                 self._idx_b[j] = g % self.ring
             self._copy(3, self._gath_p, self._cache_p, self._bytes, len(idx), self._seq, self._idx_b, self.B, self.ring, main)
 
-    def head(self, f: int, e: int, descs, slot: int):
-        """Head of expression e on the gathered taps of frame f; its mask into the device buffer at the offset of descs[e]."""
+    def head(self, f: int, e: int, descs, slot: int, describe: Optional[DescribePlan] = None):
+        """Head of expression e on the gathered taps of frame f; its mask into the device buffer at the offset of descs[e]; with
+        `describe`, row e of the frame's describe tail: frame f's own tap among the gathered ones weighted by the head's sigm."""
         torch, m = self.torch, self.model
         words, sl = self.words[e]
         with torch.no_grad(), torch.cuda.device(self.dev):
             o = m.head_video(self.gathered, words, sl)
+            if describe is not None:
+                _enqueue_describe(self, self.gathered[self.describe[1]], self.own, o["sigm"].float().reshape(1, m.H, m.W).data_ptr(),
+                                  o["score_c4"], o["score_c5"], describe, e, 1)
             if self.dcrf:
                 from . import crf
                 sigm = o["sigm"].float().reshape(1, m.H, m.W)
@@ -499,13 +629,15 @@ class _ClipStage:
             _lib.call("cmpc_eval_mask_out", score.data_ptr(), dt, 1, m.H, m.W, float(thr), self.C.byref(descs[e]), self.mask_dev.data_ptr(),
                       self.mask_dev.numel(), self.value, torch.cuda.current_stream(self.dev).cuda_stream)
 
-    def finish(self, f: int, slot: int, nbytes: int, jf: Optional[JfPlan] = None):
+    def finish(self, f: int, slot: int, nbytes: int, jf: Optional[JfPlan] = None, describe: Optional[DescribePlan] = None):
         """Frame f's masks (every expression) into pinned slot `slot`, its event behind the copy; with `jf`, their J / F counts
-        behind them."""
+        behind them; with `describe`, the tail the frame's heads wrote behind those."""
         torch = self.torch
         with torch.cuda.device(self.dev):
             if jf is not None:
                 nbytes = _enqueue_scoring(self, jf, nbytes)
+            if describe is not None:
+                nbytes = describe.end
             self.host[slot][:nbytes].copy_(self.mask_dev[:nbytes], non_blocking=True)
             self.events[slot].record(torch.cuda.current_stream(self.dev))
 
@@ -541,11 +673,17 @@ class ClipSegmenter:
 
     run(..., ground_truth=fn, jf=None, seq=None) scores the masks on the device as FrameSegmenter.run does: fn(e, f) is called for
     e = 0 .. E - 1 when frame f's heads are enqueued, one cmpc_mask_jf call per frame scores its annotated expressions, and the counts
-    reach `jf` (self.jf) under sequence (seq, e) and frame f."""
+    reach `jf` (self.jf) under sequence (seq, e) and frame f.
+
+    describe= / describe_weights= / run(..., pivots=) describe every (frame, expression) as FrameSegmenter does: behind each head
+    cmpc_mask_pool pools frame f's own tap (position FRAME_IDX.index(frames // 2) of the gathered set) weighted by the head's sigm,
+    "hard" weights being sigm >= threshold with score="sigm" and sigm >= 0.5 otherwise, and cmpc_level_agree counts the agreement of
+    score_c4 and score_c5; they reach self.pivots under sequence (seq, e) and frame f (a second run() into the same log under the same
+    seq raises, as in FrameSegmenter)."""
 
     def __init__(self, model, vocab=None, score: str = "up", threshold: float = 1e-9, out_size: Callable[[int, int], Tuple[int, int]] = full_size,
                  value: int = 255, dcrf: bool = False, dcrf_method: str = "lattice", ring: int = 32, depth: int = 2, copy: bool = True,
-                 _stage=None, lookahead: Optional[int] = None):
+                 _stage=None, lookahead: Optional[int] = None, describe: Optional[str] = None, describe_weights: str = "soft"):
         from .model import FRAME_IDX
         if not getattr(model, "video", False):
             raise ValueError("ClipSegmenter: expects the video model (CMPC_video_mm_tgraph_allvec); use FrameSegmenter for the image models")
@@ -570,8 +708,15 @@ class ClipSegmenter:
         self.nslots = self.depth + 1
         self.stats = {"frames": 0, "backbone_passes": 0, "gathers": 0, "heads": 0}
         self.jf, self.bound_th = None, 0.008
-        self.stage = _stage if _stage is not None else _ClipStage(model, self.ring, self.nslots, self.score, self.threshold, self.value,
-                                                                  self.dcrf, self.dcrf_method)
+        self.describe, self.describe_weights, self.pivots = describe, describe_weights, None
+        level = check_describe(model, describe, describe_weights)
+        if _stage is not None:
+            self.stage = _stage
+        elif level is None:
+            self.stage = _ClipStage(model, self.ring, self.nslots, self.score, self.threshold, self.value, self.dcrf, self.dcrf_method)
+        else:
+            self.stage = _ClipStage(model, self.ring, self.nslots, self.score, self.threshold, self.value, self.dcrf, self.dcrf_method,
+                                    describe=(describe_weights, level))
 
     def _frame(self, f: int, im) -> Tuple[np.ndarray, Tuple[int, int]]:
         try:
@@ -584,7 +729,7 @@ class ClipSegmenter:
         return a, (int(oh), int(ow))
 
     def run(self, frames: Iterable, expressions: Sequence, ground_truth: Optional[Callable] = None, jf: Optional[HU.JFEval] = None,
-            seq=None) -> Iterator[Tuple[int, int, np.ndarray]]:
+            seq=None, pivots: Optional[HU.PivotLog] = None) -> Iterator[Tuple[int, int, np.ndarray]]:
         exprs = [check_expression(i, ex, self.vocab, self.T) for i, ex in enumerate(expressions)]
         if not exprs:
             raise ValueError("ClipSegmenter.run: no expressions")
@@ -593,9 +738,13 @@ class ClipSegmenter:
         if len(exprs) > MAX_BATCH:
             raise ValueError("ClipSegmenter.run: %d expressions, at most %d per run" % (len(exprs), MAX_BATCH))
         st, B, E = self.stage, self.B, len(exprs)
+        C = None                                   # channels of the described tap
+        if self.describe is not None:
+            self.pivots = pivots if pivots is not None else HU.PivotLog()
+            C = st.describe_channels()
         stats = self.stats = {"frames": 0, "backbone_passes": 0, "gathers": 0, "heads": 0}
         free = deque(range(self.nslots))
-        pending = deque()                          # (slot, frame, descs, scoring plan) in enqueue order = yield order
+        pending = deque()                          # (slot, frame, descs, scoring plan, describe plan) in enqueue order = yield order
         sizes = deque()                            # out sizes of the frames read whose heads are not enqueued yet
         it = iter(frames)
         st.set_expressions(exprs)
@@ -603,12 +752,15 @@ class ClipSegmenter:
 
         def hand_out(block: bool):
             while pending and (block or st.done(pending[0][0])):
-                slot, fr, descs, plan = pending.popleft()
+                slot, fr, descs, plan, dplan = pending.popleft()
                 st.wait(slot)
                 host = st.view(slot)
                 if plan is not None:
                     for e, c in zip(plan.idx, slot_counts(host, plan)):
                         self.jf.add((seq, e), fr, c)
+                if dplan is not None:
+                    for e, (iu, d, a) in enumerate(zip(*slot_describe(host, dplan))):
+                        self.pivots.add((seq, e), fr, d, a, iu)
                 for e, d in enumerate(descs):
                     mk = host[d.offset: d.offset + d.h * d.w].reshape(d.h, d.w)
                     yield e, fr, (mk.copy() if self.copy else mk)
@@ -648,7 +800,10 @@ class ClipSegmenter:
             # frame f + ahead was read, or the video ended and `read` is its length
             idx = sampled_frames(f, read, self.frames)
             descs, nbytes = plan_masks([sizes.popleft()] * E, self.H, self.W)
-            st.reserve(nbytes if ground_truth is None else scored_bytes(nbytes, E))
+            if C is None:
+                st.reserve(nbytes if ground_truth is None else scored_bytes(nbytes, E))
+            else:
+                st.reserve(plan_describe(nbytes, 0 if ground_truth is None else E, E, C).end)
             if not free:
                 yield from hand_out(True)
             slot = free.popleft()
@@ -657,16 +812,23 @@ class ClipSegmenter:
                 gts = [(e, ground_truth(e, f)) for e in range(E)]
                 plan = plan_scoring(descs, [(e, check_ground_truth(e, f, g, (descs[e].h, descs[e].w))) for e, g in gts if g is not None],
                                     nbytes, self.bound_th)
+            # head() and finish() keep their older call shapes while describe= (and ground_truth=) are off, as in FrameSegmenter.run
+            dplan = None if C is None else plan_describe(nbytes, 0 if plan is None else plan.n, E, C)
             st.gather(f, idx)
             stats["gathers"] += 1
             for e in range(E):
-                st.head(f, e, descs, slot)
+                if dplan is None:
+                    st.head(f, e, descs, slot)
+                else:
+                    st.head(f, e, descs, slot, describe=dplan)
                 stats["heads"] += 1
-            if ground_truth is None:
+            if dplan is not None:
+                st.finish(f, slot, nbytes, jf=plan, describe=dplan)
+            elif ground_truth is None:
                 st.finish(f, slot, nbytes)
             else:
                 st.finish(f, slot, nbytes, jf=plan)
-            pending.append((slot, f, descs, plan))
+            pending.append((slot, f, descs, plan, dplan))
             f += 1
             stats["frames"] = f
             yield from hand_out(False)

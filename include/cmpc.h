@@ -662,6 +662,31 @@ int cmpc_mask_jf_workspace(const cmpc_jf_desc* descs_host, int B, int64_t* bytes
 int cmpc_mask_jf(const unsigned char* pred, int64_t pred_bytes, const unsigned char* gt, int64_t gt_bytes,
                  const cmpc_jf_desc* descs_host, int B, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- Pivot frames (test.py:150-181, 289-307): what the reference's find_pivot_frames and its per-frame consistency score need from
+ *      the device.  Everything is validated before anything is launched; n in 1..CMPC_EVAL_MAX_BATCH results per call; no allocation
+ *      or synchronisation.
+ *      cmpc_mask_pool: "global feature of each frame = (mask * visual_feature)":
+ *        desc[i, c] = sum_{y, x} wgt_i[y, x] * feat_i[y, x, c]      area[i] = sum_{y, x} wgt_i[y, x]
+ *        wgt_i[y, x] = score_i[y * (sH / h), x * (sW / w)] (CMPC_POOL_SOFT), or that float32 >= thresh ? 1 : 0 (CMPC_POOL_HARD, test.py:307)
+ *      feat: result i's NHWC tap [h, w, C] of storage type dt (0 f32, 1 bf16, 2 f16) at feat + i * feat_stride elements (feat_stride a
+ *      multiple of 8 that is >= h * w * C), 16-byte aligned, C % 8 == 0, h * w <=
+ *      CMPC_POOL_MAX_POSITIONS.  score: float32 [n, sH, sW], sH % h == 0 and sW % w == 0; no exp is taken: pass the sigmoid.  desc
+ *      float32 [n, C], area float32 [n].  Products and sums are float32 in a fixed order (positions in chunks of CMPC_POOL_CHUNK, the
+ *      chunks' partial rows added in order; no floating-point atomics): reruns are bit-identical and a result does not depend on the
+ *      results beside it.  ws: device scratch of cmpc_mask_pool_workspace's size, 16-byte aligned; nothing but desc, area and ws is
+ *      written.  |desc - exact| <= (h w + 1) 2^-24 sum |wgt * feat| (tests/pivot_ref.py restates the sums in float64).
+ *      cmpc_level_agree: counts[i] = {I, U} = the sizes of (a_i > t) & (b_i > t) and (a_i > t) | (b_i > t) for two float32 maps
+ *      [n, h, w] -- loss.iou_with_threshold (util/loss.py:51-68) on logits, t = log(p / (1 - p)) of its probability threshold.  The
+ *      call clears the n x 2 words on the stream and then writes them; exact integers, whatever the order of the work. ------------- */
+#define CMPC_POOL_SOFT 0
+#define CMPC_POOL_HARD 1
+#define CMPC_POOL_CHUNK 64
+#define CMPC_POOL_MAX_POSITIONS (1 << 21)
+int cmpc_mask_pool_workspace(int n, int h, int w, int C, int64_t* bytes);
+int cmpc_mask_pool(int dt, const void* feat, int64_t feat_stride, const float* score, int sH, int sW, int n, int h, int w, int C,
+                   int mode, float thresh, float* desc, float* area, void* ws, int64_t ws_bytes, void* stream);
+int cmpc_level_agree(const float* a, const float* b, int n, int h, int w, float thresh, uint64_t* counts, void* stream);
+
 /* ---- The drivers' pictures (the `-v` switch of trainval_model.py:306-330 and CMPC_video/trainval_video.py, the panels of
  *      test_visualize_fusion*.py:283-304 and test_visualize_graph.py:267-274) rendered on the device.  Packed buffers are described by
  *      cmpc_eval_desc (offset, h, w, c; the geometry fields count only where stated).  Descriptors are HOST memory, validated before
