@@ -50,7 +50,9 @@ __global__ __launch_bounds__(256) void crf_filter_kernel(const float2* __restric
                 const float dr = (float)(c & 255u) - r0, dg = (float)((c >> 8) & 255u) - g0, db = (float)(c >> 16) - b0;
                 k *= __builtin_amdgcn_exp2f(-cl2 * (dr * dr + dg * dg + db * db));
             }
-            if (v) { const float2 q = v[row + xx]; t0 += k * q.x; t1 += k * q.y; }
+            // explicit fma for both labels: left to contraction, the compiler merged `t0 += k * q.x` with the `t0 += k` below into a
+            // rounded product plus an add and fused only t1, so the labels rounded differently (p = 0.5 everywhere drifted to label 0)
+            if (v) { const float2 q = v[row + xx]; t0 = fmaf(k, q.x, t0); t1 = fmaf(k, q.y, t1); }
             else t0 += k;
         }
         s0 += wy * t0; s1 += wy * t1;

@@ -73,16 +73,21 @@ def embed(f):
 class Lattice:
     """The lattice of one feature set: slice table (off, w), blur neighbours nb [d+1, M, 2] (M = absent -> a zero row)."""
 
-    def __init__(self, f):
+    def __init__(self, f, fast=False):
         N, d = f.shape
         keys, w = embed(f)
+        self.d, self.N = d, N
+        self.w = w.astype(np.float64)
+        self.alpha = 1.0 / (1.0 + 2.0 ** -d)
+        if fast:
+            self._number_sorted(keys)
+            return
         index = {}
         off = np.empty((N, d + 1), np.int64)
         for p in range(N):
             for r in range(d + 1):
                 off[p, r] = index.setdefault(tuple(keys[p, r]), len(index))
-        self.d, self.N, self.M = d, N, len(index)
-        self.off, self.w = off, w.astype(np.float64)
+        self.M, self.off = len(index), off
         vk = np.array(list(index.keys()), np.int64).reshape(self.M, d)
         nb = np.full((d + 1, self.M, 2), self.M, np.int64)
         for j in range(d + 1):
@@ -93,7 +98,38 @@ class Lattice:
                 nb[j, m, 0] = index.get(tuple(vk[m] + step), self.M)
                 nb[j, m, 1] = index.get(tuple(vk[m] - step), self.M)
         self.nb = nb
-        self.alpha = 1.0 / (1.0 + 2.0 ** -d)
+
+    def _number_sorted(self, keys):
+        """The same M, off and nb without the Python loops, for images of 10^4 pixels and more: np.unique on the keys packed into one
+        int64, renumbered by first appearance.  tests/test_crf_refs_host.py pins it to the dict version."""
+        N, d = self.N, self.d
+        flat = keys.reshape(-1, d)
+        lo = flat.min(0)
+        span = flat.max(0) - lo + 1
+        assert np.prod(span.astype(np.float64)) < 2.0 ** 62, "keys do not pack into an int64"
+        stride = np.concatenate([[1], np.cumprod(span[:-1])]).astype(np.int64)
+
+        def pack(k):
+            return ((k - lo) * stride).sum(1)
+
+        uniq, first, inv = np.unique(pack(flat), return_index=True, return_inverse=True)
+        self.M = M = len(uniq)
+        number = np.empty(M, np.int64)
+        number[np.argsort(first, kind="stable")] = np.arange(M)     # sorted position -> number in order of first appearance
+        self.off = number[inv.reshape(-1)].reshape(N, d + 1)
+        vk = np.empty((M, d), np.int64)
+        vk[number] = flat[first]
+        nb = np.full((d + 1, M, 2), M, np.int64)
+        for j in range(d + 1):
+            step = np.full(d, -1, np.int64)
+            if j < d:
+                step[j] = d
+            for side, k in enumerate((vk + step, vk - step)):
+                inside = ((k >= lo) & (k < lo + span)).all(1)       # outside the box of the keys: no such vertex (and no valid packing)
+                pk = pack(np.where(inside[:, None], k, lo))
+                pos = np.minimum(np.searchsorted(uniq, pk), M - 1)
+                nb[j, :, side] = np.where(inside & (uniq[pos] == pk), number[pos], M)
+        self.nb = nb
 
     def splat(self, v):
         """v [N, C] -> vertex values [M + 1, C] (row M stays zero)."""
@@ -116,13 +152,14 @@ class Lattice:
         return self.slice(self.blur(self.splat(v), order))
 
 
-def lattices(sigm_shape, rgb, sxy_g=3.0, sxy_b=20.0, srgb=3.0):
+def lattices(sigm_shape, rgb, sxy_g=3.0, sxy_b=20.0, srgb=3.0, fast=False):
     H, W = sigm_shape
-    return Lattice(features(H, W, None, sxy_g)), Lattice(features(H, W, rgb, sxy_b, srgb))
+    return Lattice(features(H, W, None, sxy_g), fast), Lattice(features(H, W, rgb, sxy_b, srgb), fast)
 
 
-def dense_crf(sigm, rgb, sxy_g=3.0, compat_g=3.0, sxy_b=20.0, srgb=3.0, compat_b=10.0, iters=5):
-    """oracle.dense_crf_numpy.dense_crf with K Q replaced by the lattice filter L Q: Q [2, H, W] float64."""
+def dense_crf(sigm, rgb, sxy_g=3.0, compat_g=3.0, sxy_b=20.0, srgb=3.0, compat_b=10.0, iters=5, lats=None):
+    """oracle.dense_crf_numpy.dense_crf with K Q replaced by the lattice filter L Q: Q [2, H, W] float64.  `lats`: the pair that
+    `lattices` returns for these parameters, when the caller has built it already."""
     sigm = np.asarray(sigm, dtype=np.float64)
     H, W = sigm.shape
     U = unary_from_sigmoid(sigm)
@@ -130,7 +167,7 @@ def dense_crf(sigm, rgb, sxy_g=3.0, compat_g=3.0, sxy_b=20.0, srgb=3.0, compat_b
     if iters == 0:
         return Q.reshape(2, H, W)
     terms = []
-    for w, lat in zip((compat_g, compat_b), lattices((H, W), rgb, sxy_g, sxy_b, srgb)):
+    for w, lat in zip((compat_g, compat_b), lats if lats is not None else lattices((H, W), rgb, sxy_g, sxy_b, srgb)):
         nrm = 1.0 / np.sqrt(lat.apply(np.ones((H * W, 1)))[:, 0] + 1e-20)      # symmetric normalisation, K 1 through the same lattice
         terms.append((w, lat, nrm))
     for _ in range(iters):
