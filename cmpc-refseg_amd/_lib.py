@@ -143,6 +143,16 @@ class JfDesc(C.Structure):
 
 
 JF_MAX_RADIUS = 128      # CMPC_JF_MAX_RADIUS
+
+
+class CcDesc(C.Structure):
+    """cmpc_cc_desc"""
+    _fields_ = [("off", C.c_int64), ("h", C.c_int), ("w", C.c_int)]
+
+
+CC_MAX_KEEP = 8                           # CMPC_CC_MAX_KEEP
+CC_MAX_PIXELS = 1 << 24                   # CMPC_CC_MAX_PIXELS
+CC_TILE_H, CC_TILE_W = 16, 64             # CMPC_CC_TILE_H / CMPC_CC_TILE_W
 POOL_SOFT, POOL_HARD = 0, 1               # CMPC_POOL_* modes of cmpc_mask_pool
 POOL_MODES = {"soft": POOL_SOFT, "hard": POOL_HARD}
 POOL_CHUNK = 64                           # CMPC_POOL_CHUNK: positions per partial row
@@ -269,6 +279,8 @@ SIGNATURES = {
     "cmpc_train_accuracy": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "cmpc_mask_jf_workspace": [C.POINTER(JfDesc), _I, C.POINTER(_L)],
     "cmpc_mask_jf": [_P, _L, _P, _L, C.POINTER(JfDesc), _I, _P, _P, _L, _P],
+    "cmpc_mask_components_workspace": [C.POINTER(CcDesc), _I, C.POINTER(_L)],
+    "cmpc_mask_components": [_P, _L, C.POINTER(CcDesc), _I, _I, _I, _L, _P, _P, _P, _L, _P],
     "cmpc_mask_pool_workspace": [_I, _I, _I, _I, C.POINTER(_L)],
     "cmpc_mask_pool": [_I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _L, _P],
     "cmpc_level_agree": [_P, _P, _I, _I, _I, _F, _P, _P],

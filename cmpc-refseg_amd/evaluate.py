@@ -385,6 +385,157 @@ def mask_jf(preds, gts, bound_th: float = 0.008, device="cuda:0") -> np.ndarray:
         return counts.cpu().numpy()
 
 
+# ---- connected components and mask cleaning: cmpc_mask_components (include/cmpc.h; hostutil.clean_mask is the host twin) ---------------
+CC_STATS = 4                   # n_components, area, area_largest, area_kept
+
+
+def cc_descs(sizes: Sequence[Tuple[int, int]], offs: Sequence[int]):
+    """cmpc_cc_desc[n] of [h, w] masks at byte offsets `offs`."""
+    _check_batch(len(sizes))
+    d = (_lib.CcDesc * len(sizes))()
+    for i, ((h, w), o) in enumerate(zip(sizes, offs)):
+        if int(h) * int(w) > _lib.CC_MAX_PIXELS:
+            raise ValueError("mask %d: %d x %d exceeds %d pixels" % (i, h, w, _lib.CC_MAX_PIXELS))
+        d[i] = _lib.CcDesc(int(o), int(h), int(w))
+    return d
+
+
+def cc_workspace(descs, n: int) -> int:
+    """cmpc_mask_components_workspace: 64 + 64 n + 8 * sum roundup(h w, 4) bytes."""
+    import ctypes
+    out = ctypes.c_int64()
+    _lib.call("cmpc_mask_components_workspace", descs, n, ctypes.byref(out))
+    return out.value
+
+
+class _CcDevice:
+    """The device half of cleaning, shared by mask_components / mask_clean and the two segmenters: cmpc_mask_components works on the
+    masks where they lie and writes the statistics (and labels) where it is told, on the current stream.  The workspace grows only
+    when a call needs more than any before it (reserve() ahead of the steady state)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.ws = None
+
+    def reserve(self, nbytes: int):
+        if self.ws is None or self.ws.numel() * 4 < nbytes:
+            with torch.cuda.device(self.device):
+                self.ws = torch.empty(max(-(-nbytes // 4), 1 << 16), dtype=torch.int32, device=self.device)
+
+    def run(self, mask_ptr: int, mask_bytes: int, descs, n: int, connectivity: int, keep: int, min_area: int, stats_ptr: int,
+            labels_ptr: Optional[int] = None, ws_bytes: Optional[int] = None):
+        with torch.cuda.device(self.device):
+            self.reserve(cc_workspace(descs, n) if ws_bytes is None else ws_bytes)
+            _lib.call("cmpc_mask_components", mask_ptr, mask_bytes, descs, n, int(connectivity), int(keep), int(min_area), labels_ptr,
+                      stats_ptr, self.ws.data_ptr(), self.ws.numel() * 4, torch.cuda.current_stream(self.device).cuda_stream)
+
+    def status(self) -> torch.Tensor:
+        """The status word of the last call, as a one-element view of the workspace (read it behind a synchronisation)."""
+        return self.ws[:1]
+
+
+_CC_DEVICE: Dict[str, _CcDevice] = {}
+
+
+def _components(masks, connectivity: int, keep: int, min_area: int, device, want_labels: bool, who: str):
+    keep, min_area, connectivity = HU.check_clean(keep, min_area, connectivity)
+    masks = list(masks)
+    if not masks:
+        raise ValueError("%s: no masks" % who)
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    # everything is validated on the host before the first device call
+    host = {}
+    for i, m in enumerate(masks):
+        if torch.is_tensor(m):
+            if m.device != dev or m.dtype != torch.uint8 or m.dim() != 2 or not m.is_contiguous() or m.numel() == 0:
+                raise ValueError("mask %d: a tensor must be a contiguous uint8 [h, w] on %s, got %s %s on %s"
+                                 % (i, dev, m.dtype, tuple(m.shape), m.device))
+            hw = int(m.shape[0]) * int(m.shape[1])
+        else:
+            try:
+                host[i] = _masks_u8([m])[0]
+            except ValueError as e:
+                raise ValueError("mask %d: %s" % (i, str(e).split(": ", 1)[-1])) from None
+            hw = host[i].size
+        if hw > _lib.CC_MAX_PIXELS:
+            raise ValueError("mask %d: %d pixels, at most %d" % (i, hw, _lib.CC_MAX_PIXELS))
+    key = str(dev)
+    if key not in _CC_DEVICE:
+        _CC_DEVICE[key] = _CcDevice(dev)
+    cd = _CC_DEVICE[key]
+    n = len(masks)
+    out: list = [None] * n
+    later = []                                     # (device copy of a chunk's results, [(mask index, first element, h, w)])
+    with torch.cuda.device(dev):
+        stats = torch.empty(n, CC_STATS, dtype=torch.int64, device=dev)
+        status = torch.zeros(-(-n // MAX_BATCH), dtype=torch.int32, device=dev)
+        for c, s in enumerate(range(0, n, MAX_BATCH)):
+            idx = list(range(s, min(s + MAX_BATCH, n)))
+            sizes = [tuple(int(v) for v in (host[i].shape if i in host else masks[i].shape)) for i in idx]
+            offs, off = {}, 0
+            for i in idx:
+                if i in host:
+                    offs[i] = _Offset(off)
+                    off += -(-host[i].size // _ALIGN) * _ALIGN
+            up = _staging(dev, "cc").upload([host[i] for i in idx if i in host], [offs[i] for i in idx if i in host], off) if offs else None
+            addr = [up.data_ptr() + offs[i].offset if i in host else masks[i].data_ptr() for i in idx]
+            base = min(addr)
+            nbytes = max(a + h * w for a, (h, w) in zip(addr, sizes)) - base
+            descs = cc_descs(sizes, [a - base for a in addr])
+            lab = torch.empty(sum(h * w for h, w in sizes), dtype=torch.int32, device=dev) if want_labels else None
+            cd.run(base, nbytes, descs, len(idx), connectivity, keep, min_area, stats[s: s + len(idx)].data_ptr(),
+                   labels_ptr=None if lab is None else lab.data_ptr())
+            status[c: c + 1].copy_(cd.status())
+            first, back = 0, []
+            for i, (h, w) in zip(idx, sizes):
+                if want_labels:
+                    if i in host:
+                        back.append((i, first, h, w))
+                    else:
+                        out[i] = lab[first: first + h * w].view(h, w)
+                    first += h * w
+                elif i in host:
+                    back.append((i, offs[i].offset, h, w))
+                else:
+                    out[i] = masks[i]
+            if back:                               # the staging slot is reused two uploads from now: keep a copy of what it holds
+                later.append((lab if want_labels else up.clone(), back))
+        out_stats = stats.cpu().numpy()            # the one synchronisation
+        if int(status.max().item()) != 0:
+            raise _lib.CmpcError("%s: cmpc_mask_components reported a loop that reached its bound (status %s): the result is not valid"
+                                 % (who, status.cpu().tolist()))
+        for t, back in later:
+            flat = t.cpu().numpy()
+            for i, o, h, w in back:
+                got = flat[o: o + h * w].reshape(h, w)
+                if want_labels:
+                    out[i] = got.copy()
+                else:                              # the uploaded copy was {0, 1}: kept pixels keep the caller's values
+                    src = np.asarray(masks[i])
+                    src = src[:, :, 0] if src.ndim == 3 else src
+                    out[i] = np.where(got != 0, src, 0).astype(src.dtype)
+    return out, out_stats
+
+
+def mask_components(masks, connectivity: int = 8, device="cuda:0") -> Tuple[list, np.ndarray]:
+    """The connected components of every [h, w] mask (non-zero = foreground; cmpc_mask_components, label-only): (labels, stats).
+    labels[i]: int32 [h, w], 0 for background and 1 + the raster index of the component's first pixel for foreground -- a NumPy array
+    for a host mask, a device tensor for a device mask; stats: int64 [n, 4] = (n_components, area, area_largest, area_kept = area).
+    Host arrays are packed and uploaded; contiguous uint8 device tensors are read in place and not written.  Arguments are validated
+    on the host before any device call.  Chunks of MAX_BATCH on the current stream, one synchronisation at the end; raises CmpcError
+    if the kernels' status word is set."""
+    return _components(masks, connectivity, 0, 0, device, True, "mask_components")
+
+
+def mask_clean(masks, keep: int = 1, min_area: int = 0, connectivity: int = 8, device="cuda:0") -> Tuple[list, np.ndarray]:
+    """Keep the `keep` largest components (0: all) of at least `min_area` pixels of every mask, as hostutil.clean_mask does on the host:
+    (cleaned masks, stats int64 [n, 4]).  A host array comes back as a new array (kept pixels keep their value); a contiguous uint8
+    device tensor is cleaned IN PLACE and returned.  Validation, chunks and synchronisation as for mask_components."""
+    return _components(masks, connectivity, keep, min_area, device, False, "mask_clean")
+
+
 # ---- pivot frames: cmpc_mask_pool and cmpc_level_agree (include/cmpc.h; hostutil.find_pivot_frames / PivotLog use what they give) ------
 _POOL_DT = {torch.float32: _lib.DT_F32, torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16}
 

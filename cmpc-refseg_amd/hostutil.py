@@ -514,3 +514,84 @@ class PivotLog:
     def meta(self, num_propagate: int = 2, nearest_first: bool = False) -> Dict[object, List[int]]:
         """{seq: pivots}: the content of test.py's meta_pivot_frames."""
         return {seq: self.pivots(seq, num_propagate, nearest_first) for seq in self.seqs}
+
+
+# ---- cleaning masks by their connected components (the host twin of cmpc_mask_components: evaluate.mask_clean, the segmenters' clean=) --
+CLEAN_MAX_KEEP = 8             # CMPC_CC_MAX_KEEP
+CLEAN_STATS = ("n_components", "area", "area_largest", "area_kept")
+
+
+def check_clean(keep, min_area, connectivity) -> Tuple[int, int, int]:
+    """(keep, min_area, connectivity) as integers; ValueError outside keep 0..8, min_area >= 0, connectivity 4 | 8."""
+    for name, v in (("keep", keep), ("min_area", min_area), ("connectivity", connectivity)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    if not 0 <= keep <= CLEAN_MAX_KEEP:
+        raise ValueError("keep = %r outside 0..%d" % (keep, CLEAN_MAX_KEEP))
+    if min_area < 0:
+        raise ValueError("min_area = %r is negative" % (min_area,))
+    if connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
+    return int(keep), int(min_area), int(connectivity)
+
+
+def clean_mask(mask, keep: int = 1, min_area: int = 0, connectivity: int = 8) -> Tuple[np.ndarray, np.ndarray]:
+    """cmpc_mask_components' rule on scipy.ndimage.label: components of the non-zero pixels of `mask` [h, w], ranked by area
+    descending with ties to the component whose first pixel comes first in raster order (SciPy numbers components in that order, so
+    a stable sort by area keeps it); one is kept iff (keep == 0 or rank < keep) and area >= min_area.  Returns (a new mask: kept
+    pixels keep their value, the rest 0; int64 stats {n_components, area, area_largest, area_kept})."""
+    from scipy import ndimage
+    keep, min_area, connectivity = check_clean(keep, min_area, connectivity)
+    a = np.asarray(mask)
+    if a.ndim != 2:
+        raise ValueError("clean_mask: expected [h, w], got %s" % (a.shape,))
+    lab, n = ndimage.label(a != 0, structure=ndimage.generate_binary_structure(2, 1 if connectivity == 4 else 2))
+    if n == 0:
+        return a.copy(), np.zeros(4, np.int64)
+    areas = np.bincount(lab.reshape(-1), minlength=n + 1)[1:]
+    order = np.argsort(-areas, kind="stable")
+    ok = np.zeros(n + 1, bool)
+    ranked = order if keep == 0 else order[:keep]
+    ok[1 + ranked[areas[ranked] >= min_area]] = True
+    kept = ok[lab]
+    return np.where(kept, a, 0).astype(a.dtype), np.array([n, areas.sum(), areas.max(), np.count_nonzero(kept)], np.int64)
+
+
+class CleanLog:
+    """What the segmenters' clean= collects, per sequence (one (video, expression) pair):
+
+        log = CleanLog(); log.add(seq, frame, stats) ...; log.fragmented(); log.dump()
+
+    stats: the four integers of cmpc_mask_components for that frame (CLEAN_STATS)."""
+
+    def __init__(self):
+        self.seqs: Dict[object, Dict[int, Tuple[int, int, int, int]]] = {}
+
+    def add(self, seq, frame: int, stats):
+        frames = self.seqs.setdefault(seq, {})
+        if frame in frames:
+            raise ValueError("CleanLog.add: sequence %r already holds frame %r" % (seq, frame))
+        s = tuple(int(v) for v in np.asarray(stats).reshape(4))
+        if min(s) < 0 or s[2] > s[1] or s[3] > s[1] or (s[0] == 0) != (s[1] == 0):
+            raise ValueError("CleanLog.add: impossible statistics %r" % (s,))
+        frames[frame] = s
+
+    def __len__(self) -> int:
+        return sum(len(f) for f in self.seqs.values())
+
+    def stats(self, seq) -> Tuple[np.ndarray, List[int]]:
+        """(int64 [F, 4] in frame order, the frame ids)."""
+        if seq not in self.seqs:
+            raise KeyError("CleanLog: no sequence %r" % (seq,))
+        ids = sorted(self.seqs[seq])
+        return np.array([self.seqs[seq][f] for f in ids], dtype=np.int64).reshape(len(ids), 4), ids
+
+    def fragmented(self, min_share: float = 0.9) -> List[Tuple[object, int]]:
+        """(seq, frame) of every frame whose largest component holds less than `min_share` of the foreground; never an empty frame."""
+        return [(seq, f) for seq, frames in self.seqs.items() for f in sorted(frames)
+                if frames[f][1] > 0 and frames[f][2] < min_share * frames[f][1]]
+
+    def dump(self) -> List[Dict[str, object]]:
+        """JSON-able: one {"seq", "frame", and the four statistics} per frame, sequences in insertion order, frames in order."""
+        return [dict(zip(CLEAN_STATS, frames[f]), seq=list(seq) if isinstance(seq, tuple) else seq, frame=int(f))
+                for seq, frames in self.seqs.items() for f in sorted(frames)]

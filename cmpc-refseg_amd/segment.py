@@ -14,6 +14,7 @@ does the same work in batches of model.batch_size frames:
     model.head on those taps                once per (frame batch, expression)
     cmpc_eval_mask_out + one copy           the batch's masks, sigm >= threshold resized and cropped to out_size(h, w), into a ring of
                                             pinned host buffers behind an event
+    (cmpc_mask_components, clean=)          between the two: the masks' largest connected components kept in place on the device
 
 with gv_norm="sample" by default (LSTM_model.set_gv_norm), so that every (expression, frame) pair gets what the batch-1 loop computes,
 whatever else shares its batch -- the pads of a short last batch included.
@@ -37,8 +38,8 @@ from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, hostutil as HU
-from .evaluate import (JF_COUNTS, MAX_BATCH, JfPlan, _check_dcrf_method, _images_u8, agree_logit, check_gv_norm, check_pool_mode, gv_norm_scope,
-                       plan_masks, plan_prep)
+from .evaluate import (CC_STATS, JF_COUNTS, MAX_BATCH, JfPlan, _check_dcrf_method, _images_u8, agree_logit, cc_descs, cc_workspace, check_gv_norm,
+                       check_pool_mode, gv_norm_scope, plan_masks, plan_prep)
 
 
 def half_size(h: int, w: int) -> Tuple[int, int]:
@@ -187,17 +188,81 @@ def _enqueue_describe(stage, tap, i0: int, sigm_ptr: int, a, b, plan: DescribePl
     stage.pooler.agree(a.data_ptr(), b.data_ptr(), n, int(a.shape[1]), int(a.shape[2]), stage.agree_logit, base + plan.off + 16 * row)
 
 
+# ---- clean=: keep the largest connected components of every mask on the device (cmpc_mask_components), for hostutil.CleanLog ------------
+def check_clean(clean) -> Optional[Tuple[int, int, int]]:
+    """clean -> (keep, min_area, connectivity), None when the option is off.  A dict or an object with some of the attributes keep
+    (default 1), min_area (0), connectivity (8); ValueError for anything else or for values hostutil.check_clean rejects."""
+    if clean is None:
+        return None
+    names = ("keep", "min_area", "connectivity")
+    if isinstance(clean, dict):
+        unknown = sorted(set(clean) - set(names))
+        if unknown:
+            raise ValueError("clean: unknown keys %s (expected some of %s)" % (unknown, list(names)))
+        get = clean.get
+    elif any(hasattr(clean, k) for k in names):
+        get = lambda k, dflt: getattr(clean, k, dflt)
+    else:
+        raise ValueError("clean must be None, a dict or an object with keep / min_area / connectivity, got %r" % (clean,))
+    return HU.check_clean(get("keep", 1), get("min_area", 0), get("connectivity", 8))
+
+
+class CleanPlan:
+    """One cmpc_mask_components call on the n packed masks of a ring slot, and where its statistics lie: int64 [n, 4] at `off`, the next
+    8-byte boundary behind whatever the slot already carries (the masks, the J / F counts, the describe tail); `end`: the bytes the
+    slot's one copy then carries."""
+    __slots__ = ("n", "descs", "keep", "min_area", "connectivity", "off", "end", "ws_bytes")
+
+    def __init__(self, descs, opts: Tuple[int, int, int], tail: int):
+        self.n = len(descs)
+        self.descs = cc_descs([(d.h, d.w) for d in descs], [d.offset for d in descs])
+        self.keep, self.min_area, self.connectivity = opts
+        self.off = clean_offset(tail)
+        self.end = self.off + 8 * CC_STATS * self.n
+        self.ws_bytes = cc_workspace(self.descs, self.n)
+
+
+def clean_offset(tail: int) -> int:
+    return -(-int(tail) // 8) * 8
+
+
+def cleaned_bytes(tail: int, n: int) -> int:
+    """Bytes of a ring slot that carries `tail` bytes and the statistics of n cleaned masks behind them."""
+    return clean_offset(tail) + 8 * CC_STATS * n
+
+
+def slot_clean(host: np.ndarray, plan: CleanPlan) -> np.ndarray:
+    """The int64 [n, 4] statistics at the tail of a pinned slot."""
+    return host[plan.off: plan.end].view(np.int64).reshape(plan.n, CC_STATS)
+
+
+def _enqueue_clean(stage, plan: CleanPlan, nbytes: int):
+    """The device half both stages share: cmpc_mask_components in place on the `nbytes` of masks cmpc_eval_mask_out left in
+    stage.mask_dev, the statistics into the same buffer at the plan's offset."""
+    base = stage.mask_dev.data_ptr()
+    stage.cleaner.run(base, nbytes, plan.descs, plan.n, plan.connectivity, plan.keep, plan.min_area, base + plan.off, ws_bytes=plan.ws_bytes)
+
+
+def _slot_tail(nbytes: int, scored: Optional[int], described: Optional[Tuple[int, int]]) -> int:
+    """The bytes a slot carries before any clean tail: `nbytes` of masks, the counts of `scored` results (None: no scoring), the
+    describe tail of described = (n, C) results."""
+    if described is not None:
+        return plan_describe(nbytes, scored or 0, described[0], described[1]).end
+    return nbytes if scored is None else scored_bytes(nbytes, scored)
+
+
 class _DeviceStage:
     """The device half of FrameSegmenter.  All buffers are allocated once (the pinned ring and the device mask buffer grow only when a
     batch needs more bytes than any before it): two feed / proc_im sets that alternate with the frame batches, one device mask buffer,
     `nslots` pinned host buffers with an event each.  Everything is enqueued on the caller's current stream."""
 
-    def __init__(self, model, nslots: int, threshold: float, value: int, dcrf: bool, dcrf_method: str, describe=None):
+    def __init__(self, model, nslots: int, threshold: float, value: int, dcrf: bool, dcrf_method: str, describe=None, clean: bool = False):
         import torch
-        from .evaluate import _JfDevice, _PoolDevice, _Staging
+        from .evaluate import _CcDevice, _JfDevice, _PoolDevice, _Staging
         self.torch = torch
         self.model, self.threshold, self.value, self.dcrf, self.dcrf_method = model, threshold, value, dcrf, dcrf_method
         self.dev = model.device
+        self.cleaner = _CcDevice(self.dev) if clean else None
         B, H, W = model.batch_size, model.H, model.W
         self.describe = describe                       # (weights, index of the tap) or None
         if describe is not None:
@@ -252,10 +317,12 @@ class _DeviceStage:
             feats, done = m.features_async(feed)
         return feats, done, feed, proc
 
-    def segment(self, token, e: int, descs, nbytes: int, slot: int, jf: Optional[JfPlan] = None, describe: Optional[DescribePlan] = None):
+    def segment(self, token, e: int, descs, nbytes: int, slot: int, jf: Optional[JfPlan] = None, describe: Optional[DescribePlan] = None,
+                clean: Optional[CleanPlan] = None):
         """Head of expression e on the batch's taps, the masks of its first len(descs) frames into ring slot `slot`; with `jf`, their
         J / F counts behind them; with `describe`, their descriptors (the batch's tap weighted by the head's sigm, with DenseCRF too:
-        the descriptor describes the network's own answer), areas and level-agreement counts behind those."""
+        the descriptor describes the network's own answer), areas and level-agreement counts behind those; with `clean`, the masks
+        are cleaned in place before they are scored, and their component statistics ride at the end."""
         torch, m = self.torch, self.model
         feats, done, feed, proc = token
         n = len(descs)
@@ -271,11 +338,15 @@ class _DeviceStage:
             dt = _lib.EVAL_F32 if score.dtype == torch.float32 else _lib.EVAL_U8
             _lib.call("cmpc_eval_mask_out", score.data_ptr(), dt, n, m.H, m.W, float(thr), descs, self.mask_dev.data_ptr(),
                       self.mask_dev.numel(), self.value, torch.cuda.current_stream(self.dev).cuda_stream)
+            if clean is not None:
+                _enqueue_clean(self, clean, nbytes)
             if jf is not None:
                 nbytes = _enqueue_scoring(self, jf, nbytes)
             if describe is not None:
                 _enqueue_describe(self, feats[self.describe[1]], 0, sigm.data_ptr(), o["score_c4"], o["score_c5"], describe, 0, n)
                 nbytes = describe.end
+            if clean is not None:
+                nbytes = clean.end
             self.host[slot][:nbytes].copy_(self.mask_dev[:nbytes], non_blocking=True)
             self.events[slot].record(torch.cuda.current_stream(self.dev))
 
@@ -312,11 +383,19 @@ class FrameSegmenter:
     area and counts travel with the masks and reach `pivots` (run(..., pivots=), a hostutil.PivotLog kept as self.pivots; a fresh one
     when none is passed) under sequence (seq, e) and frame f before the masks are yielded; the yielded triples are the same.  A log
     holds a (sequence, frame) once: a second run() with the same `pivots` and the same `seq` raises ValueError from PivotLog.add when
-    its first result is handed out -- pass a fresh log or another seq."""
+    its first result is handed out -- pass a fresh log or another seq.
+
+    clean={"keep": 1, "min_area": 0, "connectivity": 8} (a dict or an object with some of these attributes; None, the default: off)
+    cleans every mask on the device before anything else sees it: behind cmpc_eval_mask_out, cmpc_mask_components keeps the `keep`
+    largest connected components (0: all) of at least `min_area` pixels in place -- hostutil.clean_mask's rule -- so the yielded
+    masks and, with ground_truth, the J / F counts are those of the cleaned masks; describe= reads sigm and is unaffected; with dcrf
+    the DenseCRF mask is cleaned.  The statistics (n_components, area, area_largest, area_kept) of the mask BEFORE cleaning travel
+    with the masks and reach `cleaned` (run(..., cleaned=), a hostutil.CleanLog kept as self.cleaned; a fresh one when none is
+    passed) under sequence (seq, e) and frame f.  With clean=None no code path changes."""
 
     def __init__(self, model, vocab=None, threshold: float = 0.5, out_size: Callable[[int, int], Tuple[int, int]] = half_size, value: int = 255,
                  dcrf: bool = False, dcrf_method: str = "lattice", gv_norm: str = "sample", depth: int = 2, copy: bool = True, _stage=None,
-                 describe: Optional[str] = None, describe_weights: str = "soft"):
+                 describe: Optional[str] = None, describe_weights: str = "soft", clean=None):
         if getattr(model, "video", False):
             raise ValueError("FrameSegmenter: the video model (CMPC_video_mm_tgraph_allvec) is not supported: it takes a clip per forward pass")
         if model.batch_size > MAX_BATCH:
@@ -334,13 +413,11 @@ class FrameSegmenter:
         self.jf, self.bound_th = None, 0.008
         self.describe, self.describe_weights, self.pivots = describe, describe_weights, None
         level = check_describe(model, describe, describe_weights)
-        if _stage is not None:
-            self.stage = _stage
-        elif level is None:
-            self.stage = _DeviceStage(model, self.nslots, self.threshold, self.value, self.dcrf, self.dcrf_method)
-        else:
-            self.stage = _DeviceStage(model, self.nslots, self.threshold, self.value, self.dcrf, self.dcrf_method,
-                                      describe=(describe_weights, level))
+        self.clean, self.cleaned = check_clean(clean), None
+        kw = {} if level is None else {"describe": (describe_weights, level)}
+        if self.clean is not None:
+            kw["clean"] = True
+        self.stage = _stage if _stage is not None else _DeviceStage(model, self.nslots, self.threshold, self.value, self.dcrf, self.dcrf_method, **kw)
 
     def _batches(self, frames: Iterable) -> Iterator[Tuple[int, List[np.ndarray]]]:
         """(index of the first frame, the validated frames) of every batch of B, read lazily."""
@@ -368,10 +445,12 @@ class FrameSegmenter:
         return descs, nbytes
 
     def run(self, frames: Iterable, expressions: Sequence, ground_truth: Optional[Callable] = None, jf: Optional[HU.JFEval] = None,
-            seq=None, pivots: Optional[HU.PivotLog] = None) -> Iterator[Tuple[int, int, np.ndarray]]:
+            seq=None, pivots: Optional[HU.PivotLog] = None, cleaned: Optional[HU.CleanLog] = None) -> Iterator[Tuple[int, int, np.ndarray]]:
         exprs = [check_expression(i, ex, self.vocab, self.T) for i, ex in enumerate(expressions)]
         if not exprs:
             raise ValueError("FrameSegmenter.run: no expressions")
+        if self.clean is not None:
+            self.cleaned = cleaned if cleaned is not None else HU.CleanLog()
         if ground_truth is not None:
             self.jf = jf if jf is not None else HU.JFEval()
         st = self.stage
@@ -385,9 +464,12 @@ class FrameSegmenter:
         def hand_out(block: bool):
             """Yield the masks of the oldest result(s) whose event has completed (waiting for the oldest one if `block`)."""
             while pending and (block or st.done(pending[0][0])):
-                slot, e, first, descs, plan, dplan = pending.popleft()
+                slot, e, first, descs, plan, dplan, cplan = pending.popleft()
                 st.wait(slot)
                 host = st.view(slot)
+                if cplan is not None:
+                    for i, c in enumerate(slot_clean(host, cplan)):
+                        self.cleaned.add((seq, e), first + i, c)
                 if plan is not None:
                     for i, c in zip(plan.idx, slot_counts(host, plan)):
                         self.jf.add((seq, e), first + i, c)
@@ -410,10 +492,8 @@ class FrameSegmenter:
                     return None
                 first, ims = nxt
                 descs, nbytes = self._plan(first, ims)
-                if C is None:
-                    st.reserve(nbytes if ground_truth is None else scored_bytes(nbytes, len(descs)))
-                else:
-                    st.reserve(plan_describe(nbytes, 0 if ground_truth is None else len(descs), len(descs), C).end)
+                tail = _slot_tail(nbytes, None if ground_truth is None else len(descs), None if C is None else (len(descs), C))
+                st.reserve(tail if self.clean is None else cleaned_bytes(tail, len(descs)))
                 return first, descs, nbytes, st.begin(ims + [ims[0]] * (self.B - len(ims)))
 
             cur = begin_next()
@@ -426,21 +506,25 @@ class FrameSegmenter:
                     if not free:
                         yield from hand_out(True)
                     slot = free.popleft()
-                    # three call shapes on purpose: a stage written before jf= or describe= existed (the fake stages of the older host
+                    # several call shapes on purpose: a stage written before jf=, describe= or clean= existed (the fake stages of the older host
                     # tests, a caller's own _stage) keeps working as long as the options it does not know stay off
                     plan = dplan = None
                     if ground_truth is not None:
                         gts = [(i, ground_truth(e, first + i)) for i in range(len(descs))]
                         plan = plan_scoring(descs, [(i, check_ground_truth(e, first + i, g, (descs[i].h, descs[i].w)))
                                                     for i, g in gts if g is not None], nbytes, self.bound_th)
+                    kw = {}
                     if C is not None:
                         dplan = plan_describe(nbytes, 0 if plan is None else plan.n, len(descs), C)
-                        st.segment(token, e, descs, nbytes, slot, jf=plan, describe=dplan)
+                        kw = {"jf": plan, "describe": dplan}
                     elif ground_truth is not None:
-                        st.segment(token, e, descs, nbytes, slot, jf=plan)
-                    else:
-                        st.segment(token, e, descs, nbytes, slot)
-                    pending.append((slot, e, first, descs, plan, dplan))
+                        kw = {"jf": plan}
+                    cplan = None
+                    if self.clean is not None:     # the fourth shape: `clean` reaches the stage only when the option is on
+                        tail = dplan.end if dplan is not None else nbytes if plan is None else scored_bytes(nbytes, plan.n)
+                        cplan = kw["clean"] = CleanPlan(descs, self.clean, tail)
+                    st.segment(token, e, descs, nbytes, slot, **kw)
+                    pending.append((slot, e, first, descs, plan, dplan, cplan))
                     yield from hand_out(False)
                 cur = nxt
             while pending:
@@ -500,10 +584,11 @@ class _ClipStage:
     batch evicts among it), and the batch's event is recorded behind the scatter.  Gathers, heads, cmpc_eval_mask_out and the copies to
     the pinned ring run on the caller's stream; a gather waits for the event of the newest batch its clip reads."""
 
-    def __init__(self, model, ring: int, nslots: int, score: str, threshold: float, value: int, dcrf: bool, dcrf_method: str, describe=None):
+    def __init__(self, model, ring: int, nslots: int, score: str, threshold: float, value: int, dcrf: bool, dcrf_method: str, describe=None,
+                 clean: bool = False):
         import ctypes
         import torch
-        from .evaluate import _JfDevice, _PoolDevice, _Staging
+        from .evaluate import _CcDevice, _JfDevice, _PoolDevice, _Staging
         from .model import FRAME_IDX
         self.torch, self.C = torch, ctypes
         self.model, self.score, self.threshold, self.value, self.dcrf, self.dcrf_method = model, score, threshold, value, dcrf, dcrf_method
@@ -523,6 +608,7 @@ class _ClipStage:
             self.batch_ev = [torch.cuda.Event() for _ in range(ring // B + 2)]
             self.events = [torch.cuda.Event() for _ in range(nslots)]
         self.scorer = _JfDevice(self.dev)
+        self.cleaner = _CcDevice(self.dev) if clean else None
         self.describe = describe                       # (weights, index of the tap) or None
         if describe is not None:
             _check_describe_grid(model, describe[1])
@@ -629,15 +715,21 @@ class _ClipStage:
             _lib.call("cmpc_eval_mask_out", score.data_ptr(), dt, 1, m.H, m.W, float(thr), self.C.byref(descs[e]), self.mask_dev.data_ptr(),
                       self.mask_dev.numel(), self.value, torch.cuda.current_stream(self.dev).cuda_stream)
 
-    def finish(self, f: int, slot: int, nbytes: int, jf: Optional[JfPlan] = None, describe: Optional[DescribePlan] = None):
+    def finish(self, f: int, slot: int, nbytes: int, jf: Optional[JfPlan] = None, describe: Optional[DescribePlan] = None,
+               clean: Optional[CleanPlan] = None):
         """Frame f's masks (every expression) into pinned slot `slot`, its event behind the copy; with `jf`, their J / F counts
-        behind them; with `describe`, the tail the frame's heads wrote behind those."""
+        behind them; with `describe`, the tail the frame's heads wrote behind those; with `clean`, the masks are cleaned in place
+        first (so the counts score the cleaned masks) and their component statistics ride at the end."""
         torch = self.torch
         with torch.cuda.device(self.dev):
+            if clean is not None:
+                _enqueue_clean(self, clean, nbytes)
             if jf is not None:
                 nbytes = _enqueue_scoring(self, jf, nbytes)
             if describe is not None:
                 nbytes = describe.end
+            if clean is not None:
+                nbytes = clean.end
             self.host[slot][:nbytes].copy_(self.mask_dev[:nbytes], non_blocking=True)
             self.events[slot].record(torch.cuda.current_stream(self.dev))
 
@@ -679,11 +771,14 @@ class ClipSegmenter:
     cmpc_mask_pool pools frame f's own tap (position FRAME_IDX.index(frames // 2) of the gathered set) weighted by the head's sigm,
     "hard" weights being sigm >= threshold with score="sigm" and sigm >= 0.5 otherwise, and cmpc_level_agree counts the agreement of
     score_c4 and score_c5; they reach self.pivots under sequence (seq, e) and frame f (a second run() into the same log under the same
-    seq raises, as in FrameSegmenter)."""
+    seq raises, as in FrameSegmenter).
+
+    clean= / run(..., cleaned=) clean every mask on the device as FrameSegmenter does: one cmpc_mask_components call per frame on its
+    E masks, behind the heads' cmpc_eval_mask_out and before cmpc_mask_jf; the statistics reach self.cleaned under (seq, e), f."""
 
     def __init__(self, model, vocab=None, score: str = "up", threshold: float = 1e-9, out_size: Callable[[int, int], Tuple[int, int]] = full_size,
                  value: int = 255, dcrf: bool = False, dcrf_method: str = "lattice", ring: int = 32, depth: int = 2, copy: bool = True,
-                 _stage=None, lookahead: Optional[int] = None, describe: Optional[str] = None, describe_weights: str = "soft"):
+                 _stage=None, lookahead: Optional[int] = None, describe: Optional[str] = None, describe_weights: str = "soft", clean=None):
         from .model import FRAME_IDX
         if not getattr(model, "video", False):
             raise ValueError("ClipSegmenter: expects the video model (CMPC_video_mm_tgraph_allvec); use FrameSegmenter for the image models")
@@ -710,13 +805,12 @@ class ClipSegmenter:
         self.jf, self.bound_th = None, 0.008
         self.describe, self.describe_weights, self.pivots = describe, describe_weights, None
         level = check_describe(model, describe, describe_weights)
-        if _stage is not None:
-            self.stage = _stage
-        elif level is None:
-            self.stage = _ClipStage(model, self.ring, self.nslots, self.score, self.threshold, self.value, self.dcrf, self.dcrf_method)
-        else:
-            self.stage = _ClipStage(model, self.ring, self.nslots, self.score, self.threshold, self.value, self.dcrf, self.dcrf_method,
-                                    describe=(describe_weights, level))
+        self.clean, self.cleaned = check_clean(clean), None
+        kw = {} if level is None else {"describe": (describe_weights, level)}
+        if self.clean is not None:
+            kw["clean"] = True
+        self.stage = _stage if _stage is not None else _ClipStage(model, self.ring, self.nslots, self.score, self.threshold, self.value, self.dcrf,
+                                                                   self.dcrf_method, **kw)
 
     def _frame(self, f: int, im) -> Tuple[np.ndarray, Tuple[int, int]]:
         try:
@@ -729,10 +823,12 @@ class ClipSegmenter:
         return a, (int(oh), int(ow))
 
     def run(self, frames: Iterable, expressions: Sequence, ground_truth: Optional[Callable] = None, jf: Optional[HU.JFEval] = None,
-            seq=None, pivots: Optional[HU.PivotLog] = None) -> Iterator[Tuple[int, int, np.ndarray]]:
+            seq=None, pivots: Optional[HU.PivotLog] = None, cleaned: Optional[HU.CleanLog] = None) -> Iterator[Tuple[int, int, np.ndarray]]:
         exprs = [check_expression(i, ex, self.vocab, self.T) for i, ex in enumerate(expressions)]
         if not exprs:
             raise ValueError("ClipSegmenter.run: no expressions")
+        if self.clean is not None:
+            self.cleaned = cleaned if cleaned is not None else HU.CleanLog()
         if ground_truth is not None:
             self.jf = jf if jf is not None else HU.JFEval()
         if len(exprs) > MAX_BATCH:
@@ -752,9 +848,12 @@ class ClipSegmenter:
 
         def hand_out(block: bool):
             while pending and (block or st.done(pending[0][0])):
-                slot, fr, descs, plan, dplan = pending.popleft()
+                slot, fr, descs, plan, dplan, cplan = pending.popleft()
                 st.wait(slot)
                 host = st.view(slot)
+                if cplan is not None:
+                    for e, c in enumerate(slot_clean(host, cplan)):
+                        self.cleaned.add((seq, e), fr, c)
                 if plan is not None:
                     for e, c in zip(plan.idx, slot_counts(host, plan)):
                         self.jf.add((seq, e), fr, c)
@@ -800,10 +899,8 @@ class ClipSegmenter:
             # frame f + ahead was read, or the video ended and `read` is its length
             idx = sampled_frames(f, read, self.frames)
             descs, nbytes = plan_masks([sizes.popleft()] * E, self.H, self.W)
-            if C is None:
-                st.reserve(nbytes if ground_truth is None else scored_bytes(nbytes, E))
-            else:
-                st.reserve(plan_describe(nbytes, 0 if ground_truth is None else E, E, C).end)
+            tail = _slot_tail(nbytes, None if ground_truth is None else E, None if C is None else (E, C))
+            st.reserve(tail if self.clean is None else cleaned_bytes(tail, E))
             if not free:
                 yield from hand_out(True)
             slot = free.popleft()
@@ -822,13 +919,17 @@ class ClipSegmenter:
                 else:
                     st.head(f, e, descs, slot, describe=dplan)
                 stats["heads"] += 1
+            kw = {}
             if dplan is not None:
-                st.finish(f, slot, nbytes, jf=plan, describe=dplan)
-            elif ground_truth is None:
-                st.finish(f, slot, nbytes)
-            else:
-                st.finish(f, slot, nbytes, jf=plan)
-            pending.append((slot, f, descs, plan, dplan))
+                kw = {"jf": plan, "describe": dplan}
+            elif ground_truth is not None:
+                kw = {"jf": plan}
+            cplan = None
+            if self.clean is not None:             # `clean` reaches the stage only when the option is on
+                tail = dplan.end if dplan is not None else nbytes if plan is None else scored_bytes(nbytes, plan.n)
+                cplan = kw["clean"] = CleanPlan(descs, self.clean, tail)
+            st.finish(f, slot, nbytes, **kw)
+            pending.append((slot, f, descs, plan, dplan, cplan))
             f += 1
             stats["frames"] = f
             yield from hand_out(False)

@@ -662,6 +662,40 @@ int cmpc_mask_jf_workspace(const cmpc_jf_desc* descs_host, int B, int64_t* bytes
 int cmpc_mask_jf(const unsigned char* pred, int64_t pred_bytes, const unsigned char* gt, int64_t gt_bytes,
                  const cmpc_jf_desc* descs_host, int B, uint64_t* counts, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- Connected components of B uint8 masks of any sizes per call, and the usual clean-up on them: keep the largest components, drop
+ *      the small ones (the standard post-processing on Refer-YouTube-VOS / Refer-DAVIS).  csrc/ops_cc.hip states the kernels,
+ *      tests/cc_ref.py repeats the rules in NumPy.
+ *        input      [h, w] uint8 at masks + off, non-zero = foreground; connectivity 4 or 8; a component is a maximal connected set of
+ *                   foreground pixels
+ *        labels     background 0, foreground 1 + min{ y * w + x over the component's pixels }: canonical, independent of the order of
+ *                   the work (SciPy's labelling is brought to this form with one ndimage.minimum)
+ *        ranking    by area descending, ties to the smaller first-pixel index
+ *        clean      a component is kept iff (keep == 0 or its rank < keep) and its area >= min_area; kept pixels keep their byte, all
+ *                   other foreground pixels become 0, background is not written.  keep in 0..CMPC_CC_MAX_KEEP; keep == 0 &&
+ *                   min_area <= 1 is label-only: the masks are not written at all
+ *        stats[b]   {n_components, area, area_largest, area_kept}, exact integers; {0, 0, 0, 0} for an empty mask
+ *      Descriptors are HOST memory, validated before anything is launched and passed by value; B in 1..CMPC_EVAL_MAX_BATCH; h * w <=
+ *      CMPC_CC_MAX_PIXELS, so labels fit int32; offsets may be odd.  No allocation, no synchronisation; the launch count depends on
+ *      keep only (4 + max(keep, 1) kernels behind two memsets).  Nothing but stats, ws, labels (when given) and the dropped
+ *      pixels of masks is written; bytes between packed masks are not touched.  Integer atomics only: reruns are bit-identical and a
+ *      sample's result does not depend on the batch around it.  labels: NULL, or packed int32 [h, w] per sample, sample b at element
+ *      sum_{i < b} h_i * w_i, 4-byte aligned.  stats: 8-byte aligned.  ws: device scratch of cmpc_mask_components_workspace's size,
+ *      64 + 64 B + 8 * sum_b roundup(h_b * w_b, 4) bytes, 16-byte aligned.  Its first uint32 is a status word, cleared by every call: a
+ *      bounded loop of the kernels that reached its bound (none can, by the bounds' derivation) sets it and leaves instead of
+ *      spinning; callers that synchronise anyway read it back.  Tiles of CMPC_CC_TILE_H x CMPC_CC_TILE_W pixels are labelled in LDS
+ *      and merged across their borders. ------------------------------------------------------------------------------------------- */
+#define CMPC_CC_MAX_KEEP 8
+#define CMPC_CC_MAX_PIXELS (1 << 24)
+#define CMPC_CC_TILE_H 16
+#define CMPC_CC_TILE_W 64
+typedef struct {
+    int64_t off;                     /* byte offset of the [h, w] uint8 mask in `masks` */
+    int h, w;
+} cmpc_cc_desc;
+int cmpc_mask_components_workspace(const cmpc_cc_desc* descs_host, int B, int64_t* bytes);
+int cmpc_mask_components(unsigned char* masks, int64_t mask_bytes, const cmpc_cc_desc* descs_host, int B, int connectivity, int keep,
+                         int64_t min_area, int32_t* labels, uint64_t* stats, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- Pivot frames (test.py:150-181, 289-307): what the reference's find_pivot_frames and its per-frame consistency score need from
  *      the device.  Everything is validated before anything is launched; n in 1..CMPC_EVAL_MAX_BATCH results per call; no allocation
  *      or synchronisation.
