@@ -156,6 +156,17 @@ CC_TILE_H, CC_TILE_W = 16, 64             # CMPC_CC_TILE_H / CMPC_CC_TILE_W
 POOL_SOFT, POOL_HARD = 0, 1               # CMPC_POOL_* modes of cmpc_mask_pool
 POOL_MODES = {"soft": POOL_SOFT, "hard": POOL_HARD}
 POOL_CHUNK = 64                           # CMPC_POOL_CHUNK: positions per partial row
+POOL_MAX_POSITIONS = 1 << 21              # CMPC_POOL_MAX_POSITIONS
+PROP_MAX_SOURCES = 4                      # CMPC_PROP_MAX_SOURCES
+PROP_MAX_ROWS = 65535                     # CMPC_PROP_MAX_ROWS
+PROP_MIN_TEMPERATURE = 1e-6               # CMPC_PROP_MIN_TEMPERATURE
+
+
+class PropItem(C.Structure):
+    """cmpc_prop_item"""
+    _fields_ = [("tgt", C.c_int), ("nsrc", C.c_int), ("src", C.c_int * PROP_MAX_SOURCES), ("label", C.c_int * PROP_MAX_SOURCES)]
+
+
 VIS_PRED, VIS_GT = 0, 1                   # CMPC_VIS_* kinds of cmpc_vis_overlay
 VIS_SIGMOID, VIS_AUTO = 1, 2              # CMPC_VIS_* flags of cmpc_vis_heat
 
@@ -284,6 +295,9 @@ SIGNATURES = {
     "cmpc_mask_pool_workspace": [_I, _I, _I, _I, C.POINTER(_L)],
     "cmpc_mask_pool": [_I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _L, _P],
     "cmpc_level_agree": [_P, _P, _I, _I, _I, _F, _P, _P],
+    "cmpc_label_propagate_workspace": [_I, _I, _I, C.POINTER(_L)],
+    "cmpc_label_propagate": [_I, _P, _L, _I, _P, _I, C.POINTER(PropItem), _I, _I, _I, _I, _I, _F, _P, _P, _P, _L, _P],
+    "cmpc_prop_fuse": [_P, _P, _I, _I, _I, _I, _I, _F, _P, _P],
     "cmpc_vis_overlay": [_I, _P, _L, C.POINTER(EvalDesc), _P, _L, C.POINTER(EvalDesc), _I, _P, _L, C.POINTER(EvalDesc), _P],
     "cmpc_vis_heat_workspace": [_I, _I, C.POINTER(_L)],
     "cmpc_vis_heat": [_P, _I, _I, _I, C.POINTER(EvalDesc), _I, C.c_double, C.c_double, _P, _P, _L, _P, _L, C.POINTER(EvalDesc), _P, _P, _L, _P],

@@ -676,6 +676,130 @@ def level_agree(a, b, threshold: float = 0.2) -> torch.Tensor:
     return counts
 
 
+# ---- mask propagation: cmpc_label_propagate and cmpc_prop_fuse (include/cmpc.h; hostutil.propagation_plan says who receives from whom) ----
+def prop_workspace(n: int, h: int, w: int) -> int:
+    """cmpc_label_propagate_workspace: the inverse norms, n * (1 + PROP_MAX_SOURCES) * h * w floats, in bytes."""
+    import ctypes
+    out = ctypes.c_int64()
+    _lib.call("cmpc_label_propagate_workspace", int(n), int(h), int(w), ctypes.byref(out))
+    return out.value
+
+
+def prop_items(items) -> list:
+    """[(target frame, [(source frame, label index), ...]), ...] -> a list of _lib.PropItem.  ValueError for an item without sources
+    or with more than PROP_MAX_SOURCES; the indices themselves are checked by the library against the banks."""
+    out = []
+    for i, it in enumerate(items):
+        try:
+            tgt, srcs = it
+            srcs = [(int(f), int(l)) for f, l in srcs]
+        except (TypeError, ValueError):
+            raise ValueError("item %d: expected (target frame, [(source frame, label index), ...]), got %r" % (i, it)) from None
+        if not 1 <= len(srcs) <= _lib.PROP_MAX_SOURCES:
+            raise ValueError("item %d: %d sources, 1..%d are allowed" % (i, len(srcs), _lib.PROP_MAX_SOURCES))
+        p = _lib.PropItem()
+        p.tgt, p.nsrc = int(tgt), len(srcs)
+        for k, (f, l) in enumerate(srcs):
+            p.src[k], p.label[k] = f, l
+        out.append(p)
+    return out
+
+
+class _PropDevice:
+    """The device half of propagating, shared by label_propagate / prop_fuse and FrameSegmenter: both kernels read their inputs where
+    they lie and write where they are told, on the current stream.  The workspace grows only when a call needs more than any before
+    it (reserve() ahead of the steady state)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.ws = None
+
+    def reserve(self, n: int, h: int, w: int) -> int:
+        need = prop_workspace(n, h, w)
+        if self.ws is None or self.ws.numel() * 4 < need:
+            with torch.cuda.device(self.device):
+                self.ws = torch.empty(max(need // 4, 1 << 16), dtype=torch.float32, device=self.device)
+        return need
+
+    def propagate(self, feats: torch.Tensor, labels: torch.Tensor, items: list, radius: int, temperature: float, out_ptr: int, peak_ptr: int):
+        """feats: a bank [frames, h, w, C] of contiguous taps (any stride between frames); labels: contiguous float32 [L, h, w];
+        items: at most MAX_BATCH _lib.PropItem; out / peak: float32 [len(items), h, w] at out_ptr / peak_ptr (0: no peak)."""
+        frames, h, w, C = (int(x) for x in feats.shape)
+        n = len(items)
+        self.reserve(n, h, w)
+        stride = int(feats.stride(0)) if frames > 1 else h * w * C
+        arr = (_lib.PropItem * n)(*items)
+        _lib.call("cmpc_label_propagate", _POOL_DT[feats.dtype], feats.data_ptr(), stride, frames, labels.data_ptr(), int(labels.shape[0]),
+                  arr, n, h, w, C, int(radius), float(temperature), out_ptr, peak_ptr or None, self.ws.data_ptr(), self.ws.numel() * 4,
+                  torch.cuda.current_stream(self.device).cuda_stream)
+
+    def fuse(self, own_ptr: int, prop_ptr: int, n: int, h: int, w: int, H: int, W: int, alpha: float, fused_ptr: int):
+        _lib.call("cmpc_prop_fuse", own_ptr, prop_ptr, int(n), int(h), int(w), int(H), int(W), float(alpha), fused_ptr,
+                  torch.cuda.current_stream(self.device).cuda_stream)
+
+
+_PROP_DEVICE: Dict[str, _PropDevice] = {}
+
+
+def _prop_device(dev) -> _PropDevice:
+    key = str(dev)
+    if key not in _PROP_DEVICE:
+        _PROP_DEVICE[key] = _PropDevice(dev)
+    return _PROP_DEVICE[key]
+
+
+def label_propagate(feats, labels, items, radius: int = 12, temperature: float = 0.07, want_peak: bool = False):
+    """cmpc_label_propagate on device tensors: every item (target frame, [(source frame, label index), ...]) receives the labels of its
+    sources along cosine affinities between the taps, out[i, q] = sum_{s, p} softmax_{s, p}(<a_q, b_p> / temperature) * labels[l_s][p]
+    over the positions p within `radius` of q in both directions (radius < 0: the whole grid), a and b the L2-normalised vectors of
+    the target and source taps.  feats: a bank [frames, h, w, C] float32 / float16 / bfloat16, each frame a contiguous tap (a strided
+    selection is read in place); labels: float32 [L, h, w] on the same device.  Runs in chunks of MAX_BATCH items on the current
+    stream, nothing synchronises.  Returns float32 out [n, h, w], or (out, peak) with want_peak: peak[i, q] = the largest cosine among
+    q's candidates.  One workspace per device is shared by every call of this function on that device, as in mask_pool."""
+    _check_tap(feats)
+    if not torch.is_tensor(labels) or labels.device != feats.device or labels.dtype != torch.float32:
+        raise ValueError("labels must be a float32 tensor on feats' device")
+    frames, h, w, C = feats.shape
+    if labels.dim() != 3 or tuple(labels.shape[1:]) != (h, w) or labels.shape[0] < 1:
+        raise ValueError("labels %s against feats %s: [L, h, w] at the taps' grid" % (tuple(labels.shape), tuple(feats.shape)))
+    items = prop_items(items)
+    if not items:
+        raise ValueError("label_propagate: no items")
+    labels = labels.contiguous()
+    dev = feats.device
+    pd = _prop_device(dev)
+    n = len(items)
+    with torch.cuda.device(dev):
+        out = torch.empty(n, h, w, dtype=torch.float32, device=dev)
+        peak = torch.empty(n, h, w, dtype=torch.float32, device=dev) if want_peak else None
+        for s in range(0, n, MAX_BATCH):
+            k = min(MAX_BATCH, n - s)
+            pd.propagate(feats, labels, items[s: s + k], radius, temperature, out[s: s + k].data_ptr(), peak[s: s + k].data_ptr() if want_peak else 0)
+    return (out, peak) if want_peak else out
+
+
+def prop_fuse(own, prop, alpha: float) -> torch.Tensor:
+    """cmpc_prop_fuse on device tensors: (1 - alpha) * own + alpha * U(prop) for own float32 [n, H, W] and prop float32 [n, h, w], U the
+    model's legacy bilinear rule (the one that makes `up` from `pred`); alpha in [0, 1], alpha == 0 returns own's bits.  Chunks of
+    MAX_BATCH on the current stream, nothing synchronises.  Returns a new float32 tensor [n, H, W]."""
+    for name, t in (("own", own), ("prop", prop)):
+        if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != torch.float32 or t.dim() != 3 or t.numel() == 0:
+            raise ValueError("%s must be a float32 device tensor [n, rows, cols]" % name)
+    if own.device != prop.device or own.shape[0] != prop.shape[0]:
+        raise ValueError("own %s on %s and prop %s on %s: one n and one device" % (tuple(own.shape), own.device, tuple(prop.shape), prop.device))
+    own, prop = own.contiguous(), prop.contiguous()
+    n, H, W = own.shape
+    h, w = prop.shape[1:]
+    dev = own.device
+    pd = _prop_device(dev)
+    with torch.cuda.device(dev):
+        fused = torch.empty_like(own)
+        for s in range(0, n, MAX_BATCH):
+            k = min(MAX_BATCH, n - s)
+            pd.fuse(own[s: s + k].data_ptr(), prop[s: s + k].data_ptr(), k, h, w, H, W, alpha, fused[s: s + k].data_ptr())
+    return fused
+
+
 def unpack_masks(buf, descs) -> list:
     """The [h, w] views of a packed mask buffer (device tensor or NumPy array) at its descriptors' offsets."""
     if torch.is_tensor(buf):

@@ -516,6 +516,34 @@ class PivotLog:
         return {seq: self.pivots(seq, num_propagate, nearest_first) for seq in self.seqs}
 
 
+def propagation_plan(frame_ids: Sequence[int], pivots: Sequence[int], num_propagate: int = 2, max_sources: int = 4) -> Dict[int, List[int]]:
+    """Who receives from whom when masks are propagated from pivot frames: {frame: [pivot, ...]} for every frame of `frame_ids` that
+    is no pivot and has a pivot within num_propagate positions of it IN frame_ids (the list's order is the video's; the ids need not
+    be consecutive).  A frame's pivots come nearest first, a tie going to the lower frame id, at most max_sources of them; a frame
+    out of reach of every pivot is left out (find_pivot_frames leaves none when it ran with the same num_propagate).  ValueError for
+    a pivot that is not in frame_ids, a repeated frame id, num_propagate < 0 or max_sources < 1."""
+    ids = [int(f) for f in frame_ids]
+    p, k = int(num_propagate), int(max_sources)
+    if p < 0 or k < 1:
+        raise ValueError("propagation_plan: num_propagate %r must be >= 0 and max_sources %r >= 1" % (num_propagate, max_sources))
+    pos = {f: i for i, f in enumerate(ids)}
+    if len(pos) != len(ids):
+        raise ValueError("propagation_plan: frame_ids holds a frame twice")
+    piv = sorted(set(int(f) for f in pivots))
+    for f in piv:
+        if f not in pos:
+            raise ValueError("propagation_plan: pivot %r is not among the %d frame ids" % (f, len(ids)))
+    is_pivot = set(piv)
+    plan: Dict[int, List[int]] = {}
+    for f in ids:
+        if f in is_pivot:
+            continue
+        near = sorted((abs(pos[g] - pos[f]), g) for g in piv if abs(pos[g] - pos[f]) <= p)
+        if near:
+            plan[f] = [g for _, g in near[:k]]
+    return plan
+
+
 # ---- cleaning masks by their connected components (the host twin of cmpc_mask_components: evaluate.mask_clean, the segmenters' clean=) --
 CLEAN_MAX_KEEP = 8             # CMPC_CC_MAX_KEEP
 CLEAN_STATS = ("n_components", "area", "area_largest", "area_kept")

@@ -243,6 +243,70 @@ def _enqueue_clean(stage, plan: CleanPlan, nbytes: int):
     stage.cleaner.run(base, nbytes, plan.descs, plan.n, plan.connectivity, plan.keep, plan.min_area, base + plan.off, ws_bytes=plan.ws_bytes)
 
 
+# ---- propagate=: keep what a mask propagator needs while run() goes, then carry the pivot frames' answers to their neighbours ------------
+PROPAGATE_LEVELS = ("c4", "c5")                # taps at the head's own grid (vf_h x vf_w) on every model
+
+
+class PropOptions:
+    """FrameSegmenter(propagate=...) checked and completed: level, radius, temperature, alpha, num_propagate, bank, results."""
+    __slots__ = ("level", "radius", "temperature", "alpha", "num_propagate", "bank", "results")
+    DEFAULTS = {"level": None, "radius": 12, "temperature": 0.07, "alpha": 0.5, "num_propagate": 2, "bank": 128, "results": 512}
+
+    def tap(self) -> int:
+        return DESCRIBE_LEVELS.index(self.level)
+
+
+def check_propagate(model, propagate, describe: Optional[str]) -> Optional[PropOptions]:
+    """propagate -> PropOptions, None when the option is off.  A dict or an object with some of the attributes level ("c4" or "c5";
+    default: the describe level when that is one of the two, else "c4"), radius (12; negative: the whole grid), temperature (0.07),
+    alpha (0.5), num_propagate (2), bank (128 frames), results (512 (expression, frame) pairs); ValueError for anything else."""
+    if propagate is None:
+        return None
+    names = tuple(PropOptions.DEFAULTS)
+    if isinstance(propagate, dict):
+        unknown = sorted(set(propagate) - set(names))
+        if unknown:
+            raise ValueError("propagate: unknown keys %s (expected some of %s)" % (unknown, list(names)))
+        get = propagate.get
+    elif not isinstance(propagate, (str, int, float)) and any(hasattr(propagate, k) for k in names):
+        get = lambda k, dflt: getattr(propagate, k, dflt)
+    else:
+        raise ValueError("propagate must be None, a dict or an object with some of %s, got %r" % (list(names), propagate))
+    o = PropOptions()
+    for k, dflt in PropOptions.DEFAULTS.items():
+        setattr(o, k, get(k, dflt))
+    if o.level is None:
+        o.level = describe if describe in PROPAGATE_LEVELS else "c4"
+    if o.level not in PROPAGATE_LEVELS:
+        raise ValueError("propagate: level must be 'c4' or 'c5', got %r" % (o.level,))
+    for k in ("radius", "num_propagate", "bank", "results"):
+        v = getattr(o, k)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("propagate: %s must be an integer, got %r" % (k, v))
+        setattr(o, k, int(v))
+    if o.num_propagate < 0 or o.bank < 1 or o.results < 1:
+        raise ValueError("propagate: num_propagate %d must be >= 0, bank %d and results %d >= 1" % (o.num_propagate, o.bank, o.results))
+    try:
+        o.temperature, o.alpha = float(o.temperature), float(o.alpha)
+    except (TypeError, ValueError):
+        raise ValueError("propagate: temperature and alpha must be numbers, got %r and %r" % (o.temperature, o.alpha)) from None
+    if not (_lib.PROP_MIN_TEMPERATURE <= o.temperature < float("inf")):
+        raise ValueError("propagate: temperature must be finite and >= %g, got %r" % (_lib.PROP_MIN_TEMPERATURE, o.temperature))
+    if not 0.0 <= o.alpha <= 1.0:
+        raise ValueError("propagate: alpha must lie in [0, 1], got %r" % (o.alpha,))
+    return o
+
+
+def _consecutive_runs(idx: Sequence[int]) -> List[Tuple[int, int]]:
+    """(first position, length) of every run of consecutive values in idx."""
+    runs, s = [], 0
+    for i in range(1, len(idx) + 1):
+        if i == len(idx) or idx[i] != idx[i - 1] + 1:
+            runs.append((s, i - s))
+            s = i
+    return runs
+
+
 def _slot_tail(nbytes: int, scored: Optional[int], described: Optional[Tuple[int, int]]) -> int:
     """The bytes a slot carries before any clean tail: `nbytes` of masks, the counts of `scored` results (None: no scoring), the
     describe tail of described = (n, C) results."""
@@ -256,9 +320,10 @@ class _DeviceStage:
     batch needs more bytes than any before it): two feed / proc_im sets that alternate with the frame batches, one device mask buffer,
     `nslots` pinned host buffers with an event each.  Everything is enqueued on the caller's current stream."""
 
-    def __init__(self, model, nslots: int, threshold: float, value: int, dcrf: bool, dcrf_method: str, describe=None, clean: bool = False):
+    def __init__(self, model, nslots: int, threshold: float, value: int, dcrf: bool, dcrf_method: str, describe=None, clean: bool = False,
+                 propagate: Optional[PropOptions] = None):
         import torch
-        from .evaluate import _CcDevice, _JfDevice, _PoolDevice, _Staging
+        from .evaluate import _CcDevice, _JfDevice, _PoolDevice, _PropDevice, _Staging
         self.torch = torch
         self.model, self.threshold, self.value, self.dcrf, self.dcrf_method = model, threshold, value, dcrf, dcrf_method
         self.dev = model.device
@@ -280,6 +345,59 @@ class _DeviceStage:
         self.mask_dev = None
         self.k = 0
         self.words = []
+        self.prop = propagate
+        if propagate is not None:                      # the banks, once: taps per frame, sigm and its point samples per (expression, frame)
+            cfg = model.cfg
+            h, w, C = cfg.vf_h, cfg.vf_w, _tap_channels(model, propagate.tap())
+            if H % h or W % w or C % 8:
+                raise ValueError("propagate: a %d x %d score map over a %d x %d tap of %d channels: the map must be a multiple of the tap "
+                                 "grid and the channels a multiple of 8" % (H, W, h, w, C))
+            tdt = {_lib.DT_F32: torch.float32, _lib.DT_BF16: torch.bfloat16, _lib.DT_F16: torch.float16}[model.dt]
+            with torch.cuda.device(self.dev):
+                self.tap_bank = torch.empty(propagate.bank, h, w, C, dtype=tdt, device=self.dev)
+                self.sigm_bank = torch.empty(propagate.results, H, W, dtype=torch.float32, device=self.dev)
+                self.label_bank = torch.empty(propagate.results, h, w, dtype=torch.float32, device=self.dev)
+                self.prop_out = torch.empty(B, h, w, dtype=torch.float32, device=self.dev)
+                self.fused = torch.empty(B, H, W, dtype=torch.float32, device=self.dev)
+            self.propagator = _PropDevice(self.dev)
+            self.propagator.reserve(B, h, w)
+
+    def bank(self, feats, sigm, e: int, n: int, where: Tuple[int, int]):
+        """Keep what propagate_batch() reads: the chosen tap of the batch's n real frames (once per frame batch, with expression 0) at
+        their frame ids, and expression e's sigm and its point samples at results e * F + frame.  where = (first frame, F)."""
+        first, F = where
+        fy, fx = self.model.H // self.tap_bank.shape[1], self.model.W // self.tap_bank.shape[2]
+        if e == 0:
+            self.tap_bank[first: first + n].copy_(feats[self.prop.tap()].reshape((-1,) + tuple(self.tap_bank.shape[1:]))[:n])
+        r = e * F + first
+        self.sigm_bank[r: r + n].copy_(sigm[:n])
+        self.label_bank[r: r + n].copy_(sigm[:n, ::fy, ::fx])
+
+    def propagate_batch(self, e: int, frames: Sequence[int], sources: Sequence[Sequence[int]], F: int, descs, nbytes: int, slot: int,
+                        jf: Optional[JfPlan] = None, clean: Optional[CleanPlan] = None):
+        """Frames `frames` (ascending, at most a batch) of expression e receive from their pivots `sources`: cmpc_label_propagate on the
+        banks, cmpc_prop_fuse with each frame's own sigm, then cmpc_eval_mask_out, clean= and scoring as segment() enqueues them, into
+        ring slot `slot` behind its event."""
+        from .evaluate import prop_items
+        torch, m, o = self.torch, self.model, self.prop
+        n = len(frames)
+        h, w = int(self.tap_bank.shape[1]), int(self.tap_bank.shape[2])
+        items = prop_items([(f, [(p, e * F + p) for p in src]) for f, src in zip(frames, sources)])
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            self.propagator.propagate(self.tap_bank, self.label_bank, items, o.radius, o.temperature, self.prop_out.data_ptr(), 0)
+            for i0, k in _consecutive_runs(list(frames)):          # a frame's own sigm is read where it lies: one call per run of frames
+                self.propagator.fuse(self.sigm_bank[e * F + frames[i0]].data_ptr(), self.prop_out[i0].data_ptr(), k, h, w, m.H, m.W, o.alpha,
+                                     self.fused[i0].data_ptr())
+            _lib.call("cmpc_eval_mask_out", self.fused.data_ptr(), _lib.EVAL_F32, n, m.H, m.W, float(self.threshold), descs,
+                      self.mask_dev.data_ptr(), self.mask_dev.numel(), self.value, torch.cuda.current_stream(self.dev).cuda_stream)
+            if clean is not None:
+                _enqueue_clean(self, clean, nbytes)
+            if jf is not None:
+                nbytes = _enqueue_scoring(self, jf, nbytes)
+            if clean is not None:
+                nbytes = clean.end
+            self.host[slot][:nbytes].copy_(self.mask_dev[:nbytes], non_blocking=True)
+            self.events[slot].record(torch.cuda.current_stream(self.dev))
 
     def reserve(self, nbytes: int):
         """Room for `nbytes` of packed masks in every ring slot and in the device buffer."""
@@ -318,7 +436,7 @@ class _DeviceStage:
         return feats, done, feed, proc
 
     def segment(self, token, e: int, descs, nbytes: int, slot: int, jf: Optional[JfPlan] = None, describe: Optional[DescribePlan] = None,
-                clean: Optional[CleanPlan] = None):
+                clean: Optional[CleanPlan] = None, propagate: Optional[Tuple[int, int]] = None):
         """Head of expression e on the batch's taps, the masks of its first len(descs) frames into ring slot `slot`; with `jf`, their
         J / F counts behind them; with `describe`, their descriptors (the batch's tap weighted by the head's sigm, with DenseCRF too:
         the descriptor describes the network's own answer), areas and level-agreement counts behind those; with `clean`, the masks
@@ -330,6 +448,8 @@ class _DeviceStage:
         with torch.no_grad(), torch.cuda.device(self.dev):
             o = m.head(feats, words, sl, after=done, im=feed)
             sigm = o["sigm"].float().reshape(m.batch_size, m.H, m.W)
+            if propagate is not None:
+                self.bank(feats, sigm, e, n, propagate)
             if self.dcrf:
                 from . import crf
                 score, thr = crf.dense_crf_batch(sigm[:n], proc[:n], device=self.dev, method=self.dcrf_method), 0.5
@@ -391,11 +511,21 @@ class FrameSegmenter:
     masks and, with ground_truth, the J / F counts are those of the cleaned masks; describe= reads sigm and is unaffected; with dcrf
     the DenseCRF mask is cleaned.  The statistics (n_components, area, area_largest, area_kept) of the mask BEFORE cleaning travel
     with the masks and reach `cleaned` (run(..., cleaned=), a hostutil.CleanLog kept as self.cleaned; a fresh one when none is
-    passed) under sequence (seq, e) and frame f.  With clean=None no code path changes."""
+    passed) under sequence (seq, e) and frame f.  With clean=None no code path changes.
+
+    propagate={"level": "c4", "radius": 12, "temperature": 0.07, "alpha": 0.5, "num_propagate": 2, "bank": 128, "results": 512} (a dict
+    or an object with some of these attributes; None, the default: off) keeps what a mask propagator needs while run() goes -- run()
+    yields exactly what it yields without it.  In device banks allocated once: per frame the chosen tap (level: "c4" or "c5", default
+    the describe level, else "c4"), per (expression, frame) the head's float32 sigm [H, W] and its label, the point sample
+    sigm[y * (H / h), x * (W / w)] that cmpc_mask_pool uses (H % h == 0 and W % w == 0 as there).  The video's length must be known
+    before any work: a `frames` without len() is read into a list first, and run() raises ValueError when the video exceeds `bank`
+    frames or expressions x frames exceed `results`.  Afterwards seg.propagate(pivots) carries the pivot frames' answers to their
+    neighbours (see there).  Not with dcrf=True (ValueError): fusing happens before a CRF, and that is not built.  With propagate=None
+    no code path changes."""
 
     def __init__(self, model, vocab=None, threshold: float = 0.5, out_size: Callable[[int, int], Tuple[int, int]] = half_size, value: int = 255,
                  dcrf: bool = False, dcrf_method: str = "lattice", gv_norm: str = "sample", depth: int = 2, copy: bool = True, _stage=None,
-                 describe: Optional[str] = None, describe_weights: str = "soft", clean=None):
+                 describe: Optional[str] = None, describe_weights: str = "soft", clean=None, propagate=None):
         if getattr(model, "video", False):
             raise ValueError("FrameSegmenter: the video model (CMPC_video_mm_tgraph_allvec) is not supported: it takes a clip per forward pass")
         if model.batch_size > MAX_BATCH:
@@ -417,6 +547,11 @@ class FrameSegmenter:
         kw = {} if level is None else {"describe": (describe_weights, level)}
         if self.clean is not None:
             kw["clean"] = True
+        self.prop, self._prop_run, self.prop_jf, self.prop_cleaned = check_propagate(model, propagate, describe), None, None, None
+        if self.prop is not None:
+            if self.dcrf:
+                raise ValueError("FrameSegmenter(propagate=..., dcrf=True): fusing happens before a CRF, which is not built; use dcrf=False")
+            kw["propagate"] = self.prop
         self.stage = _stage if _stage is not None else _DeviceStage(model, self.nslots, self.threshold, self.value, self.dcrf, self.dcrf_method, **kw)
 
     def _batches(self, frames: Iterable) -> Iterator[Tuple[int, List[np.ndarray]]]:
@@ -454,6 +589,14 @@ class FrameSegmenter:
         if ground_truth is not None:
             self.jf = jf if jf is not None else HU.JFEval()
         st = self.stage
+        F = None                                   # frames of the video: known ahead only when the banks of propagate= must hold them
+        if self.prop is not None:
+            frames = frames if hasattr(frames, "__len__") else list(frames)
+            F = len(frames)
+            if F > self.prop.bank or len(exprs) * F > self.prop.results:
+                raise ValueError("FrameSegmenter.run: %d frames x %d expressions exceed the banks of propagate= (bank = %d frames, results = %d)"
+                                 % (F, len(exprs), self.prop.bank, self.prop.results))
+            self._prop_run = {"F": F, "E": len(exprs), "seq": seq, "sizes": []}
         C = None                                   # channels of the described tap
         if self.describe is not None:
             self.pivots = pivots if pivots is not None else HU.PivotLog()
@@ -492,6 +635,8 @@ class FrameSegmenter:
                     return None
                 first, ims = nxt
                 descs, nbytes = self._plan(first, ims)
+                if F is not None:
+                    self._prop_run["sizes"].extend((d.h, d.w) for d in descs)
                 tail = _slot_tail(nbytes, None if ground_truth is None else len(descs), None if C is None else (len(descs), C))
                 st.reserve(tail if self.clean is None else cleaned_bytes(tail, len(descs)))
                 return first, descs, nbytes, st.begin(ims + [ims[0]] * (self.B - len(ims)))
@@ -523,12 +668,89 @@ class FrameSegmenter:
                     if self.clean is not None:     # the fourth shape: `clean` reaches the stage only when the option is on
                         tail = dplan.end if dplan is not None else nbytes if plan is None else scored_bytes(nbytes, plan.n)
                         cplan = kw["clean"] = CleanPlan(descs, self.clean, tail)
+                    if F is not None:              # the fifth: the stage keeps the taps, sigm and labels of (e, first .. first + n - 1)
+                        kw["propagate"] = (first, F)
                     st.segment(token, e, descs, nbytes, slot, **kw)
                     pending.append((slot, e, first, descs, plan, dplan, cplan))
                     yield from hand_out(False)
                 cur = nxt
             while pending:
                 yield from hand_out(True)
+
+    def propagate(self, pivots, ground_truth: Optional[Callable] = None, jf: Optional[HU.JFEval] = None, cleaned: Optional[HU.CleanLog] = None,
+                  seq=None) -> Iterator[Tuple[int, int, np.ndarray]]:
+        """Carry the pivot frames' answers of the last run() to their neighbours (needs FrameSegmenter(propagate=...), and run()
+        consumed to its end).  pivots: a hostutil.PivotLog that holds the sequences (seq, e) as run() logs them (seq: this call's, or
+        the run's when None) -- its pivots(.., num_propagate) are taken -- or a dict {e: [frame, ...]}.  For every expression e and
+        every frame f of hostutil.propagation_plan(range(F), pivots of e, num_propagate, 4), in batches of model.batch_size frames of
+        one expression: cmpc_label_propagate carries the pivots' labels (the point samples of their sigm) to f along the banked taps,
+        cmpc_prop_fuse blends the result with f's own sigm (alpha), and the fused map goes through cmpc_eval_mask_out with f's own
+        descriptor, threshold and out_size, then clean= and scoring exactly as run() enqueues them, into the same pinned ring behind
+        events.  Yields (e, f, mask) for those frames only, expressions in order and frames ascending; pivot frames and frames out of
+        reach keep the masks run() gave.  ground_truth / jf / cleaned as in run(); the counts and statistics go to `jf` / `cleaned`
+        (fresh logs when None: a log holds a (sequence, frame) once) kept as self.prop_jf / self.prop_cleaned."""
+        if self.prop is None or self._prop_run is None:
+            raise RuntimeError("FrameSegmenter.propagate: run() has not been called with propagate= (FrameSegmenter(..., propagate={...}))")
+        o, st, run = self.prop, self.stage, self._prop_run
+        F, E, sizes = run["F"], run["E"], run["sizes"]
+        if len(sizes) != F:
+            raise RuntimeError("FrameSegmenter.propagate: run() saw %d of its %d frames: consume it to its end first" % (len(sizes), F))
+        seq = run["seq"] if seq is None else seq
+        plans = []
+        for e in range(E):
+            if isinstance(pivots, HU.PivotLog):
+                piv = pivots.pivots((seq, e), o.num_propagate)
+            else:
+                try:
+                    piv = [int(f) for f in pivots[e]]
+                except (KeyError, IndexError, TypeError):
+                    raise ValueError("FrameSegmenter.propagate: no pivots for expression %d" % e) from None
+            plans.append(HU.propagation_plan(range(F), piv, o.num_propagate, _lib.PROP_MAX_SOURCES))
+        if self.clean is not None:
+            self.prop_cleaned = cleaned if cleaned is not None else HU.CleanLog()
+        if ground_truth is not None:
+            self.prop_jf = jf if jf is not None else HU.JFEval()
+        free = deque(range(self.nslots))
+        pending = deque()                          # (slot, e, frames, descs, scoring plan, clean plan) in enqueue order = yield order
+
+        def hand_out(block: bool):
+            while pending and (block or st.done(pending[0][0])):
+                slot, e, fr, descs, plan, cplan = pending.popleft()
+                st.wait(slot)
+                host = st.view(slot)
+                if cplan is not None:
+                    for f, c in zip(fr, slot_clean(host, cplan)):
+                        self.prop_cleaned.add((seq, e), f, c)
+                if plan is not None:
+                    for i, c in zip(plan.idx, slot_counts(host, plan)):
+                        self.prop_jf.add((seq, e), fr[i], c)
+                for f, d in zip(fr, descs):
+                    mk = host[d.offset: d.offset + d.h * d.w].reshape(d.h, d.w)
+                    yield e, f, (mk.copy() if self.copy else mk)
+                free.append(slot)
+                block = False
+
+        for e, plan_e in enumerate(plans):
+            todo = sorted(plan_e)
+            for s in range(0, len(todo), self.B):
+                fr = todo[s: s + self.B]
+                descs, nbytes = plan_masks([sizes[f] for f in fr], self.H, self.W)
+                plan = None
+                if ground_truth is not None:
+                    gts = [(i, ground_truth(e, f)) for i, f in enumerate(fr)]
+                    plan = plan_scoring(descs, [(i, check_ground_truth(e, fr[i], g, (descs[i].h, descs[i].w))) for i, g in gts if g is not None],
+                                        nbytes, self.bound_th)
+                tail = nbytes if plan is None else scored_bytes(nbytes, plan.n)
+                cplan = None if self.clean is None else CleanPlan(descs, self.clean, tail)
+                st.reserve(tail if cplan is None else cplan.end)
+                if not free:
+                    yield from hand_out(True)
+                slot = free.popleft()
+                st.propagate_batch(e, fr, [plan_e[f] for f in fr], F, descs, nbytes, slot, jf=plan, clean=cplan)
+                pending.append((slot, e, fr, descs, plan, cplan))
+                yield from hand_out(False)
+        while pending:
+            yield from hand_out(True)
 
 
 # ---- CMPC_video_mm_tgraph_allvec over whole videos (CMPC_video/trainval_video.py:186-253 applied to every frame) --------------------------
@@ -774,7 +996,10 @@ class ClipSegmenter:
     seq raises, as in FrameSegmenter).
 
     clean= / run(..., cleaned=) clean every mask on the device as FrameSegmenter does: one cmpc_mask_components call per frame on its
-    E masks, behind the heads' cmpc_eval_mask_out and before cmpc_mask_jf; the statistics reach self.cleaned under (seq, e), f."""
+    E masks, behind the heads' cmpc_eval_mask_out and before cmpc_mask_jf; the statistics reach self.cleaned under (seq, e), f.
+
+    Mask propagation from pivot frames (FrameSegmenter's propagate= and propagate()) is out of scope here: the video model already
+    sees five frames of a clip per answer, and its ring of cached taps evicts frames that a propagator would still read."""
 
     def __init__(self, model, vocab=None, score: str = "up", threshold: float = 1e-9, out_size: Callable[[int, int], Tuple[int, int]] = full_size,
                  value: int = 255, dcrf: bool = False, dcrf_method: str = "lattice", ring: int = 32, depth: int = 2, copy: bool = True,

@@ -721,6 +721,40 @@ int cmpc_mask_pool(int dt, const void* feat, int64_t feat_stride, const float* s
                    int mode, float thresh, float* desc, float* area, void* ws, int64_t ws_bytes, void* stream);
 int cmpc_level_agree(const float* a, const float* b, int n, int h, int w, float thresh, uint64_t* counts, void* stream);
 
+/* ---- Mask propagation from pivot frames (what find_pivot_frames' result is for, test.py:150-181; the reference has no propagator):
+ *      non-parametric label propagation along dense correspondences between backbone taps.  Everything is validated before anything is
+ *      launched; n in 1..CMPC_EVAL_MAX_BATCH items per call, described in HOST memory and passed by value; no allocation or
+ *      synchronisation.
+ *      cmpc_label_propagate: for item i, target position q = (y, x) and the candidates (s, p = (y', x')) of the item's sources with
+ *      |y' - y| <= radius and |x' - x| <= radius (clipped at the borders; radius < 0: the whole grid),
+ *        a_q = f_q * rsqrt(max(sum f_q^2, 1e-12)), b_p likewise (a zero vector stays zero), c = <a_q, b_p>,
+ *        w = softmax over all candidates of all sources of c / temperature, out[i, q] = sum w * label_s[p], peak[i, q] = max c
+ *      feat: a bank [frames, h, w, C] of NHWC taps of storage type dt (0 f32, 1 bf16, 2 f16), frame_stride elements between frames (a
+ *      multiple of 8 that is >= h * w * C), 16-byte aligned, C % 8 == 0, h * w <= CMPC_POOL_MAX_POSITIONS; labels: float32
+ *      [n_labels, h, w]; out float32 [n, h, w]; peak float32 [n, h, w] or NULL; temperature finite and >= CMPC_PROP_MIN_TEMPERATURE;
+ *      h <= CMPC_PROP_MAX_ROWS.  Products and sums are
+ *      float32 (MFMA for every type); the softmax runs online in a fixed candidate order; no floating-point atomics: reruns are
+ *      bit-identical and an item's result does not depend on the items beside it.  ws: device scratch of
+ *      cmpc_label_propagate_workspace's size (the inverse norms, n * (1 + CMPC_PROP_MAX_SOURCES) * h * w floats), 16-byte aligned;
+ *      nothing but out, peak and ws is written.  tests/propagate_ref.py restates it in float64 and derives the bound.
+ *      cmpc_prop_fuse: fused[n, H, W] = (1 - alpha) * own + alpha * U(prop), own float32 [n, H, W], prop float32 [n, h, w], alpha in
+ *      [0, 1]; U is the legacy bilinear rule that makes `up` from `pred` (src = dst * (h / H), lo = floor(src),
+ *      hi = min(lo + 1, h - 1), all float32).  alpha == 0 copies own bit for bit.  fused may be own. ------------------------------ */
+#define CMPC_PROP_MAX_SOURCES 4
+#define CMPC_PROP_MAX_ROWS 65535              /* h of cmpc_label_propagate: a grid row is a workgroup row of the launch */
+#define CMPC_PROP_MIN_TEMPERATURE 1e-6f       /* logits |c / temperature| <= ~1e6 stay finite; a smaller one is rejected */
+typedef struct {
+    int tgt;                                  /* target frame in the feature bank */
+    int nsrc;                                 /* 1..CMPC_PROP_MAX_SOURCES */
+    int src[CMPC_PROP_MAX_SOURCES];           /* source frames in the feature bank */
+    int label[CMPC_PROP_MAX_SOURCES];         /* each source's map in the label bank */
+} cmpc_prop_item;
+int cmpc_label_propagate_workspace(int n, int h, int w, int64_t* bytes);
+int cmpc_label_propagate(int dt, const void* feat, int64_t frame_stride, int frames, const float* labels, int n_labels,
+                         const cmpc_prop_item* items_host, int n, int h, int w, int C, int radius, float temperature,
+                         float* out, float* peak, void* ws, int64_t ws_bytes, void* stream);
+int cmpc_prop_fuse(const float* own, const float* prop, int n, int h, int w, int H, int W, float alpha, float* fused, void* stream);
+
 /* ---- The drivers' pictures (the `-v` switch of trainval_model.py:306-330 and CMPC_video/trainval_video.py, the panels of
  *      test_visualize_fusion*.py:283-304 and test_visualize_graph.py:267-274) rendered on the device.  Packed buffers are described by
  *      cmpc_eval_desc (offset, h, w, c; the geometry fields count only where stated).  Descriptors are HOST memory, validated before
